@@ -3,6 +3,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload batch|single]
                     [--kernel auto|plane|pencil] [--per-gpu B] [--length L]
+                    [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json metric "GCUPS + achieved HBM GB/s, 256^3 cube"):
   batch  (default) -- configs[4]: "4096 independent 256^3 triples sharded across
@@ -19,10 +20,19 @@ process starts the N rank processes itself (RANK/LOCAL_RANK/WORLD_SIZE set
 before any of them touches the GPU; this parent never does) and exits with
 their status.
 
-Rank 0 also times single cubes (configs[1..3] and the paper's Table III sizes
+A plain run sets up, warms up, times the K steps and prints the line; its
+roofline figures come from the live kernel time and the committed PMC profile.
+--dump-outputs DIR also writes what the last timed step computed: DIR/scores.npy,
+the gathered scores of all ranks in global triple order (float64; the inputs
+are the same synthetic triples on every run, so two builds compare score for
+score).
+
+With --full, rank 0 first runs itself under rocprofv3 (N=1, the profiled
+roofline), also times single cubes (configs[1..3] and the paper's Table III sizes
 128^3 / 512^3, "single_cube"), checks a sample of the gathered scores against
 the CPU oracle ("parity") and, at N=1, times the oracle on a bounded sample of
-the same workload on every host core the job may use ("cpu_baseline").
+the same workload on every host core the job may use ("cpu_baseline"); the
+full record goes to --record-file.
 
 Prints exactly one JSON line on rank 0 (stdout); progress goes to stderr.
 """
@@ -312,6 +322,12 @@ def parse_args(argv=None):
     ap.add_argument("--kernel", choices=["auto", "plane", "pencil"], default="auto")
     ap.add_argument("--per-gpu", type=int, default=512)
     ap.add_argument("--length", type=int, default=256)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's gathered scores to DIR/scores.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the rocprofv3 child, the single "
+                         "cubes, the split over devices, the oracle parity check and the CPU baseline "
+                         "(the options below steer those legs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra-configs", action="store_true",
                     help="skip the single-cube timings other than configs[2]")
@@ -470,6 +486,8 @@ def run_rank(args, world: int, rank: int, local_rank: int, backend: str, make_ba
 
     rec = None
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, all_scores)
         rec = report(args, tsa, synth, hot, dev, world, n_total, per_gpu, n, L, params, gcups,
                      ms_per_step, kernel_ms_per_step, all_scores, extras, prof)
         rec["config"]["devices"] = devices
@@ -482,6 +500,25 @@ def run_rank(args, world: int, rank: int, local_rank: int, backend: str, make_ba
         dist.barrier()
         dist.destroy_process_group()
     return rec
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir: str, all_scores) -> None:
+    """--dump-outputs: the timed path's output after its last timed step --
+    the int32 scores its caller receives, gathered over the ranks in global
+    triple order -- as DIR/scores.npy (float64: every int32 exactly). A batch
+    beyond DUMP_MAX_BYTES is cut to a fixed seeded sample of its triples
+    (DIR/scores_index.npy names them)."""
+    os.makedirs(out_dir, exist_ok=True)
+    scores = np.asarray(all_scores, dtype=np.float64)
+    keep = DUMP_MAX_BYTES // 16  # 8 bytes of score + 8 of index per triple
+    if scores.size > keep:
+        idx = np.sort(np.random.default_rng(0).choice(scores.size, keep, replace=False))
+        np.save(os.path.join(out_dir, "scores_index.npy"), idx.astype(np.float64))
+        scores = scores[idx]
+    np.save(os.path.join(out_dir, "scores.npy"), scores)
 
 
 def report(args, tsa, synth, hot, dev, world, n_total, per_gpu, n, L, params, gcups, ms_per_step,
@@ -615,13 +652,15 @@ def compact_record(rec: dict, args) -> dict:
     written to --record-file and named under `record_file`."""
     full = json.loads(json.dumps(rec))
     path = os.path.abspath(args.record_file or os.path.join(ROOT, "gpurun_out", "bench_record.json"))
-    try:
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        with open(path, "w") as f:
-            json.dump(full, f, indent=1)
-        rel = os.path.relpath(path, ROOT) if path.startswith(ROOT) else path
-    except OSError as e:
-        rel = f"not written: {e}"
+    rel = None  # a plain run writes a record only where --record-file names one
+    if args.record_file or getattr(args, "full", False):
+        try:
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            with open(path, "w") as f:
+                json.dump(full, f, indent=1)
+            rel = os.path.relpath(path, ROOT) if path.startswith(ROOT) else path
+        except OSError as e:
+            rel = f"not written: {e}"
     single = rec.pop("single_cube", None) or {}
     configs = (rec.get("parity") or {}).get("configs", {})
     compact, timing = {}, None
@@ -1067,13 +1106,13 @@ def main(argv=None):
     if args.profile_child:
         sys.exit(profile_child_main(args))
     prof = None
-    if world == 1 and not args.no_profile:
+    if args.full and world == 1 and not args.no_profile:
         # before this process touches the GPU: the same workload under
         # rocprofv3 on this box, for the line's profiled roofline
         prof = run_profile_child(args)
         if prof.get("error"):
             log("profile child:", prof["error"])
-    rec = run_rank(args, world, rank, local_rank, "nccl", GpuBatch, prof=prof)
+    rec = run_rank(args, world, rank, local_rank, "nccl", GpuBatch, extras=args.full, prof=prof)
     if rec is not None:
         print(json.dumps(rec), flush=True)
         par = rec.get("parity")

@@ -17,7 +17,7 @@ if [ -n "$PKGS$HPKGS" ]; then
   TAG=$TAG bash scripts/gpu_ab.sh > $O/ab.out 2>&1; rc=$?; echo "ab rc=$rc"; cat $O/ab.out; [ $rc -eq 0 ] || exit $rc
 fi
 if [ -z "$NOBENCH" ]; then
-  timeout -k 10 600 python bench.py --no-profile --record-file "$GRAFT_REPO_ROOT/$O/bench_record.json" ${BENCH_ARGS} \
+  timeout -k 10 600 python bench.py --full --no-profile --record-file "$O/bench_record.json" ${BENCH_ARGS} \
     > $O/bench.json 2> $O/bench.err
   rc=$?; echo "bench rc=$rc"; cut -c1-3000 $O/bench.json; [ $rc -eq 0 ] || { tail -20 $O/bench.err; exit $rc; }
 fi

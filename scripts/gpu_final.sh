@@ -16,6 +16,6 @@ if [ -z "$NOTEST" ]; then
     > $O/pytest_gpu.log 2>&1
   rc=$?; echo "pytest rc=$rc"; tail -3 $O/pytest_gpu.log; [ $rc -eq 0 ] || exit $rc
 fi
-timeout -k 10 600 python bench.py --profile-dir "$GRAFT_REPO_ROOT/$O/bench_profile" \
+timeout -k 10 600 python bench.py --full --profile-dir "$O/bench_profile" \
   --record-file "$O/bench_record.json" ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err
 rc=$?; echo "bench rc=$rc"; cat $O/bench.json; [ $rc -eq 0 ] || { tail -20 $O/bench.err; exit $rc; }

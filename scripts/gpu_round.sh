@@ -12,7 +12,7 @@ if [ -z "$NOTEST" ]; then
     > $O/pytest_gpu.log 2>&1
   rc=$?; echo "pytest rc=$rc"; tail -3 $O/pytest_gpu.log; [ $rc -eq 0 ] || exit $rc
 fi
-timeout -k 10 600 python bench.py --profile-dir "$GRAFT_REPO_ROOT/$O/bench_profile" ${BENCH_ARGS} \
+timeout -k 10 600 python bench.py --full --profile-dir "$O/bench_profile" ${BENCH_ARGS} \
   > $O/bench.json 2> $O/bench.err
 rc=$?; echo "bench rc=$rc"; cat $O/bench.json; [ $rc -eq 0 ] || { tail -20 $O/bench.err; exit $rc; }
 [ -n "$NOPROF" ] && exit 0

@@ -241,9 +241,7 @@ def test_batch_devices_argument_checks(tsa):
 
 def test_cli_reports_no_device_or_score():
     cli = os.path.join(PKG_DIR, "bin", "tsa")
-    dat = "/root/reference/dat"
-    if not os.path.isdir(dat):
-        pytest.skip("reference not mounted")
+    dat = os.path.join(ROOT, "tests", "golden", "dat")  # the reference's dat triple
     r = subprocess.run([cli, f"{dat}/A_seq.dat", f"{dat}/B_seq.dat", f"{dat}/C_seq.dat"],
                        capture_output=True, text=True)
     if r.returncode == 0:

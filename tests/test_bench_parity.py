@@ -156,6 +156,23 @@ def test_fallback_summary_flags_any_fallback():
     assert bench.split_devices(1) == "0,0" and bench.split_devices(4) == "0,1,2,3"
 
 
+def test_plain_run_options_and_dump(tmp_path):
+    """A plain run has --full off, writes no record file unless one is named,
+    and --dump-outputs stores the gathered int32 scores exactly, as float64."""
+    import argparse
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 3 and a.warmup == 1
+    assert bench.parse_args(["--full", "--dump-outputs", "d"]).full is True
+    scores = np.array([3, -7, 2 ** 31 - 1, -2 ** 31], dtype=np.int32)
+    bench.dump_outputs(str(tmp_path / "d"), scores)
+    got = np.load(tmp_path / "d" / "scores.npy")
+    assert got.dtype == np.float64 and got.tolist() == [float(v) for v in scores]
+    out = bench.compact_record({"metric": "m", "single_cube": {}},
+                               argparse.Namespace(record_file=None, full=False))
+    assert out["record_file"] is None and list(out)[-1] == "single_cube"
+
+
 def test_line_ends_with_compact_single_cube(tmp_path):
     """the driver keeps only the tail of stdout, so the line
     ends with every single cube's time in compact form; the full record (plans,

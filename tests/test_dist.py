@@ -77,7 +77,7 @@ def test_shard_ranges_cover_exactly(tsa):
 
 
 @pytest.mark.parametrize("per_gpu", [3, 4])
-def test_bench_spawn_world2_gloo(tsa, orc, per_gpu):
+def test_bench_spawn_world2_gloo(tsa, orc, per_gpu, tmp_path):
     """bench.py's own N>1 path: spawn_ranks starts 2 rank processes with the
     torch.distributed env set, run_rank shards contiguously, times between
     barriers, takes the max over ranks and all-gathers the scores; rank 0
@@ -91,12 +91,14 @@ def test_bench_spawn_world2_gloo(tsa, orc, per_gpu):
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "tests", "_bench_cpu_rank.py"),
                         "--gpus", "2", "--per-gpu", str(per_gpu), "--length", "12",
-                        "--steps", "2", "--warmup", "1"],
+                        "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "dump")],
                        capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
     rec = json.loads(lines[0])
+    # --dump-outputs: rank 0 writes every rank's scores, in global order
+    assert np.load(tmp_path / "dump" / "scores.npy").tolist() == [float(v) for v in rec["gathered"]]
     assert rec["n_gpus"] == 2 and rec["config"]["world_size"] == 2
     assert rec["config"]["triples_total"] == 2 * per_gpu and rec["scaling"] == "weak"
     assert rec["steps"] == 2 and rec["value"] > 0

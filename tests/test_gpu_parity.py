@@ -62,15 +62,14 @@ def test_golden_final_states(gpu, golden):
         assert s == c["score"] and list(fin) == c["final7"], c["name"]
 
 
-def test_testbench_input_and_dat_cli(gpu, golden):
+def test_testbench_input_and_dat_cli(gpu, golden, tmp_path):
     z = [0] * 64
     assert gpu.score(z, z, z) == 192                       # src/TriAlign_tb.sv:423-1960
     by = {c["name"]: c for c in golden}
     t = gpu.TriAlign()
     assert t.run(by["dat"]["a"], by["dat"]["b"], by["dat"]["c"]) == 1 and t.finish
     cli = os.path.join(os.path.dirname(gpu.LIB_PATH), "..", "bin", "tsa")
-    d = os.path.join(os.environ.get("TMPDIR", "/tmp"), "tsa_dat")
-    os.makedirs(d, exist_ok=True)
+    d = str(tmp_path)
     for k in "abc":
         with open(os.path.join(d, f"{k}.dat"), "w") as f:
             f.write("\r\n".join(str(v) for v in by["dat"][k]) + "\r\n")

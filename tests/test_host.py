@@ -13,9 +13,8 @@ def test_read_dat_crlf(tsa, tmp_path):
 
 
 def test_read_reference_dat_files(tsa, golden):
-    d = "/root/reference/dat"
-    if not os.path.isdir(d):
-        pytest.skip("reference not mounted")
+    # the reference's dat/{A,B,C}_seq.dat, byte for byte (CRLF line ends)
+    d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dat")
     by = {c["name"]: c for c in golden}
     for f, k in (("A_seq.dat", "a"), ("B_seq.dat", "b"), ("C_seq.dat", "c")):
         assert list(tsa.read_sequence(os.path.join(d, f))) == by["dat"][k]
@@ -106,8 +105,10 @@ def test_ram128_image_round_trip(tsa, tmp_path):
 def test_testbench_initial_block_reader(tsa, orc, tmp_path):
     """The testbench's own input format: `seqA_ram[w][hi:lo] <= SYM;` writes in
     an initial block (src/TriAlign_tb.sv:423-1960). A synthetic block in that
-    form round-trips; when the reference tree is present its testbench is read
-    directly -- all-A, A_LENGTH = 64 (src/TriAlign_tb.sv:48) -> score 192."""
+    form round-trips; so does a block laid out as the reference's testbench
+    is: the three RAMs declared, filled to all 512 symbols with A one after
+    the other and read by index afterwards, of which A_LENGTH = 64
+    (src/TriAlign_tb.sv:48) are used -> score 192."""
     rng = np.random.default_rng(4)
     s = rng.integers(0, 5, 70).astype(np.uint8)
     names = "ATCGN"
@@ -116,11 +117,17 @@ def test_testbench_initial_block_reader(tsa, orc, tmp_path):
     f = tmp_path / "tb.sv"
     f.write_text("initial begin\n" + "\n".join(lines) + "\nend\n")
     assert np.array_equal(tsa.read_sequence(str(f), ram="seqB_ram"), s)
-    tb = "/root/reference/src/TriAlign_tb.sv"
-    if os.path.exists(tb):
-        seqs = [tsa.read_sequence(tb, ram=f"seq{k}_ram", length=64) for k in "ABC"]
-        assert all(len(x) == 64 and not x.any() for x in seqs)
-        assert orc.score(*seqs) == 192
+    decl = [f"\treg [127:0] seq{k}_ram [0:15];" for k in "ABC"]
+    fill = [f"seq{k}_ram[{i // 32}][{4 * (i % 32) + 3}:{4 * (i % 32)}] <= A;"
+            for k in "ABC" for i in range(512)]
+    use = [f"\t\t\t{k}_word <= seq{k}_ram[{k}_idx];" for k in "ABC"]
+    tb = tmp_path / "full_tb.sv"
+    tb.write_text("\n".join(decl + ["initial begin"] + fill + ["end", "always @(posedge clk) begin"]
+                            + use + ["end"]) + "\n")
+    seqs = [tsa.read_sequence(str(tb), ram=f"seq{k}_ram", length=64) for k in "ABC"]
+    assert all(len(x) == 64 and not x.any() for x in seqs)
+    assert orc.score(*seqs) == 192
+    assert len(tsa.read_sequence(str(tb), ram="seqC_ram")) == 512
 
 
 def test_pack2_layout(tsa):
