@@ -64,11 +64,11 @@ EXPORTS = (
     "tsa_device_count", "tsa_strerror", "tsa_version", "tsa_describe_plan", "tsa_align_gpu",
     "tsa_fallback_count", "tsa_check_fallback_count", "tsa_score_batch_async_p2", "tsa_pack2",
     "tsa_score_gpu_multi", "tsa_score_batch_devices", "tsa_set_override", "tsa_get_overrides",
-    "tsa_kernel_launch_count",
+    "tsa_kernel_launch_count", "tsa_align_batch",
 )
 
 # Plan overrides the library accepts (tsa_set_override; include/trialign.h).
-OVERRIDES = ("lap_chunk", "lap_m", "lap_nw", "lap_spin_limit", "lap_trace", "lap_vs",
+OVERRIDES = ("align_mode", "align_tb_bytes", "lap_chunk", "lap_m", "lap_nw", "lap_spin_limit", "lap_trace", "lap_vs",
              "pencil_arith", "pencil_mode", "pencil_two", "split_serial")
 
 # Score of a triple the device could not score (include/trialign.h).
@@ -144,6 +144,8 @@ def _load_lib() -> ctypes.CDLL:
                                                             ctypes.c_char_p, ctypes.c_size_t]
     lib.tsa_align_gpu.argtypes = [u8p, ctypes.c_int32, u8p, ctypes.c_int32, u8p, ctypes.c_int32,
                                   pp, i32p, u8p, ctypes.c_int32, i32p, i32p, ctypes.c_int32]
+    lib.tsa_align_batch.argtypes = [u8p, i64p, ctypes.c_int32, pp, i32p, u8p, i32p, i32p,
+                                    ctypes.c_int32]
     lib.tsa_score_gpu_multi.argtypes = [u8p, ctypes.c_int32, u8p, ctypes.c_int32, u8p,
                                         ctypes.c_int32, pp, i32p, ctypes.c_int32, i32p,
                                         ctypes.POINTER(ctypes.c_double)]
@@ -166,7 +168,7 @@ def _load_lib() -> ctypes.CDLL:
                  "tsa_batch_workspace_size", "tsa_score_batch_async", "tsa_device_count",
                  "tsa_describe_plan", "tsa_align_gpu", "tsa_score_batch_async_p2", "tsa_pack2",
                  "tsa_score_gpu_multi", "tsa_score_batch_devices", "tsa_set_override",
-                 "tsa_get_overrides"):
+                 "tsa_get_overrides", "tsa_align_batch"):
         getattr(lib, name).restype = ctypes.c_int
     return lib
 
@@ -248,7 +250,8 @@ class overrides:
 
 
 def kernel_launch_count() -> int:
-    """Scoring-kernel launches queued since the library was loaded."""
+    """Scoring-kernel launches (and resident traceback launches, one per
+    align_batch chunk) queued since the library was loaded."""
     return int(_lib.tsa_kernel_launch_count())
 
 
@@ -359,6 +362,35 @@ def align(a, b, c, params: Optional[TsaParams] = None, device: int = 0):
                             _ptr(mv, ctypes.c_uint8), cap, ctypes.byref(n), st, device)
     _check(rc, "tsa_align_gpu")
     return int(sc.value), tuple(int(v) for v in st), mv[: n.value].copy()
+
+
+def align_batch(triples=None, params: Optional[TsaParams] = None, device: int = 0,
+                seqs: Optional[np.ndarray] = None, offsets: Optional[np.ndarray] = None) -> list:
+    """Optimal alignments of many triples in one call (tsa_align_batch): a
+    list of ``(score, start, moves)``, one per triple in the caller's order,
+    each as ``align`` returns it. Triples whose (y,z) planes fit a workgroup
+    run the resident kernel, one launch per chunk of pointer cubes; the
+    overrides ``align_mode`` and ``align_tb_bytes`` steer path and chunking."""
+    p = params or TsaParams.default()
+    if seqs is None:
+        seqs, offsets = pack_batch(triples)
+    seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = (len(offsets) - 1) // 3
+    sc = np.zeros(max(n, 1), dtype=np.int32)
+    nm = np.zeros(max(n, 1), dtype=np.int32)
+    st = np.zeros(max(3 * n, 1), dtype=np.int32)
+    mv = np.zeros(max(int(offsets[-1] - offsets[0]) if n else 0, 1), dtype=np.uint8)
+    rc = _lib.tsa_align_batch(_ptr(seqs, ctypes.c_uint8), _ptr(offsets, ctypes.c_int64), n,
+                              ctypes.byref(p), _ptr(sc, ctypes.c_int32), _ptr(mv, ctypes.c_uint8),
+                              _ptr(nm, ctypes.c_int32), _ptr(st, ctypes.c_int32), device)
+    _check(rc, "tsa_align_batch")
+    out = []
+    for i in range(n):
+        m0 = int(offsets[3 * i] - offsets[0])
+        out.append((int(sc[i]), tuple(int(v) for v in st[3 * i:3 * i + 3]),
+                    mv[m0:m0 + int(nm[i])].copy()))
+    return out
 
 
 def penalty_table(params: Optional[TsaParams] = None):

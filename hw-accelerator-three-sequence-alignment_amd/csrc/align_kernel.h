@@ -1,0 +1,39 @@
+// align_kernel.h -- host interface of batched traceback (tsa_align_batch): the
+// resident kernel (align_kernel.hip), the batch form of the TB plane sweep and
+// the batched walk (plane_kernel.hip).
+#pragma once
+
+#include "tsa_internal.h"
+
+namespace tsa {
+
+// The TB plane sweep for a batch: triple t's pointer cube starts at word
+// d_tb_off[t] of d_tb, one launch per plane serves all n triples (max_l* over
+// the batch). d_tb_off null: tsa_internal.h's form, one triple with exact
+// lengths whose cube starts at d_tb.
+int plane_launch_batch(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, int32_t max_la,
+                       int32_t max_lb, int32_t max_lc, const KParams &kp, int32_t *d_scores,
+                       int32_t *d_final7, void *d_ws, size_t ws_bytes, hipStream_t stream, uint32_t *d_tb,
+                       const int64_t *d_tb_off);
+
+// The walks of n triples in one launch, one walker (thread) per triple:
+// triple t's cube at word tb_off[t], its lengths from offs[3t..3t+3], its 7
+// final states at final7[7t]; its moves go to moves[offs[3t] ..) in forward
+// order and {moves, x0, y0, z0} to info[4t].
+__global__ void tb_walk_batch(const uint32_t *tb, const int64_t *tb_off, const int64_t *offs, int32_t n,
+                              const int32_t *final7, uint8_t *moves, int32_t *info);
+
+// The resident traceback kernel: one workgroup sweeps a whole cube in one
+// launch, its (y,z) planes in LDS. fits: lb*lc positions within the
+// workgroup's registers and both planes within LDS (la is not bounded).
+bool align_resident_fits(int32_t la, int32_t lb, int32_t lc);
+// Dynamic LDS a (la,lb,lc) triple asks for (A staged when there is room).
+size_t align_resident_lds(int32_t la, int32_t lb, int32_t lc);
+// One launch for n triples that all fit, through launch_with_lds (so
+// tsa_kernel_launch_count counts it): max_pos = the largest lb*lc and lds =
+// the largest align_resident_lds of the batch.
+int align_launch_resident(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, int64_t max_pos, size_t lds,
+                          const KParams &kp, int32_t *d_scores, int32_t *d_final7, uint32_t *d_tb,
+                          const int64_t *d_tb_off, hipStream_t stream);
+
+}  // namespace tsa

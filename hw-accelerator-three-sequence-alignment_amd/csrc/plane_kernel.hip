@@ -33,6 +33,8 @@
 // wave (fixed y and q, consecutive z) x+z is fixed, so the stores coalesce --
 // and tb_walk follows the pointers back from cell (LA,LB,LC).
 
+#include "align_kernel.h"
+#include "literal_cell.h"
 #include "tsa_internal.h"
 
 namespace tsa {
@@ -68,38 +70,6 @@ __global__ __launch_bounds__(256) void plane_face_init(uint4 *__restrict__ ws, P
     if (k < nrow) pl[k] = make_uint4(0u, 0u, 0u, 0u);               // row y = 0
     else pl[(k - nrow) * L.ldz] = make_uint4(0u, 0u, 0u, 0u);       // column z = 0
   }
-}
-
-__device__ __forceinline__ int32_t wrapv(int32_t v, int32_t sh) { return (v << sh) >> sh; }
-
-// The 7 states of a staged cell, sign-extended.
-__device__ __forceinline__ void unpack7(uint4 c, int32_t (&v)[7]) {
-  v[0] = (int16_t)(c.x & 0xFFFF);
-  v[1] = (int16_t)(c.x >> 16);
-  v[2] = (int16_t)(c.y & 0xFFFF);
-  v[3] = (int16_t)(c.y >> 16);
-  v[4] = (int16_t)(c.z & 0xFFFF);
-  v[5] = (int16_t)(c.z >> 16);
-  v[6] = (int16_t)(c.w & 0xFFFF);
-}
-
-// Literal MAX7 of one target: max_s wrap(pred[s] - pen[s] + add). With TB,
-// arg receives the lowest source index achieving it.
-template <int T, bool TB>
-__device__ __forceinline__ int32_t max7_literal(const int32_t (&pr)[7], const KParams &kp,
-                                               int32_t add, int32_t sh, uint32_t &arg) {
-  int32_t m = wrapv(pr[0] - kp.pen[T][0] + add, sh);
-  uint32_t a = 0;
-#pragma unroll
-  for (int s = 1; s < 7; ++s) {
-    const int32_t v = wrapv(pr[s] - kp.pen[T][s] + add, sh);
-    if constexpr (TB) {
-      if (v > m) a = s;
-    }
-    m = max(m, v);
-  }
-  arg = a;
-  return m;
 }
 
 // The same MAX7 on packed int16 pairs (sources 0-1, 2-3, 4-5, 6-6): 2-4
@@ -147,21 +117,17 @@ __device__ __forceinline__ uint4 lane_shr1(uint4 v, uint4 halo) {
   return make_uint4(shr1_u32(v.x, halo.x), shr1_u32(v.y, halo.y), shr1_u32(v.z, halo.z), shr1_u32(v.w, halo.w));
 }
 
-// Traceback pointer cube index of cell (x,y,z), 1-based: [y-1][x+z-2][z-1].
-__host__ __device__ inline int64_t tb_index(int32_t x, int32_t y, int32_t z, int32_t la,
-                                            int32_t lc) {
-  return ((int64_t)(y - 1) * (la + lc - 1) + (x + z - 2)) * lc + (z - 1);
-}
-
 // One launch = plane q of every triple (blockIdx.z). Block (bx, by) is the
 // tile rows y0 = ylo + TY by .. y0+TY-1, columns z0 = zt + 64 bx .. z0+63, where
 // zt is the first column any of its rows has on this plane; thread (j, r) owns
 // cell (y0 + r, z0 + j) when that cell lies on the plane and in the cube.
+// TB: triple t's pointer cube starts at word tb_off[t] of tb (0 when tb_off is
+// null: the single-triple call).
 template <bool TB, bool WRAP>
 __global__ __launch_bounds__(64 * PLANE_TY) void plane_step_kernel(
     const uint8_t *__restrict__ seqs, const int64_t *__restrict__ offs, int32_t q,
     uint4 *__restrict__ ws, PlaneLayout L, KParams kp, int32_t *__restrict__ scores,
-    int32_t *__restrict__ final7, uint32_t *__restrict__ tb) {
+    int32_t *__restrict__ final7, uint32_t *__restrict__ tb, const int64_t *__restrict__ tb_off) {
   __shared__ uint4 tile[3 * PLANE_TILE];  // [plane q-1-p][row y0-1+r][column z0-1+c]
   const int64_t t = blockIdx.z;
   const int64_t o0 = offs[3 * t], o1 = offs[3 * t + 1], o2 = offs[3 * t + 2], o3 = offs[3 * t + 3];
@@ -220,31 +186,13 @@ __global__ __launch_bounds__(64 * PLANE_TY) void plane_step_kernel(
   const int a = tsa_sym(seqs, o0 + x - 1, kp.packed), b = tsa_sym(seqs, o1 + y - 1, kp.packed),
             cc = tsa_sym(seqs, o2 + z - 1, kp.packed);
   const int32_t sh = kp.wrap_shift;
-  const int32_t sab = (a == b) ? kp.match : kp.mismatch;
-  const int32_t sbc = (b == cc) ? kp.match : kp.mismatch;
-  const int32_t sac = (a == cc) ? kp.match : kp.mismatch;
-  int32_t s3;
-  if (kp.s3_mode == TSA_S3_SOP) s3 = wrapv(sab + sbc + sac, sh);
-  else s3 = (a == b) ? ((b == cc) ? kp.s3_eq : kp.s3_ab) : kp.s3_ne;
+  int32_t sab, sbc, sac, s3;
+  literal_adds(kp, a, b, cc, sh, sab, sbc, sac, s3);
 
   int32_t S[7];
-  uint32_t g[7];
   if constexpr (TB) {  // literal int32 candidates with the argmax of each MAX7
-    int32_t pM[7], pX[7], pY[7], pZ[7], pXY[7], pYZ[7], pXZ[7];
-    unpack7(cM, pM);
-    unpack7(cX, pX);
-    unpack7(cY, pY);
-    unpack7(cZ, pZ);
-    unpack7(cXY, pXY);
-    unpack7(cYZ, pYZ);
-    unpack7(cXZ, pXZ);
-    S[SM] = max7_literal<SM, TB>(pM, kp, s3, sh, g[SM]);
-    S[SIX] = max7_literal<SIX, TB>(pX, kp, 0, sh, g[SIX]);
-    S[SIY] = max7_literal<SIY, TB>(pY, kp, 0, sh, g[SIY]);
-    S[SIZ] = max7_literal<SIZ, TB>(pZ, kp, 0, sh, g[SIZ]);
-    S[SIXY] = max7_literal<SIXY, TB>(pXY, kp, sab, sh, g[SIXY]);
-    S[SIYZ] = max7_literal<SIYZ, TB>(pYZ, kp, sbc, sh, g[SIYZ]);
-    S[SIXZ] = max7_literal<SIXZ, TB>(pXZ, kp, sac, sh, g[SIXZ]);
+    const uint32_t w = literal_cell_tb(cM, cX, cY, cZ, cXY, cYZ, cXZ, kp, s3, sab, sbc, sac, sh, S);
+    tb[(tb_off ? tb_off[t] : 0) + tb_index(x, y, z, la, lc)] = w;
   } else {  // packed int16 pairs
     const uint32_t sh2 = (uint32_t)(16 - kp.bits) * 0x00010001u;
     auto two = [](int32_t v) { return (uint32_t)(uint16_t)v * 0x00010001u; };
@@ -264,14 +212,7 @@ __global__ __launch_bounds__(64 * PLANE_TY) void plane_step_kernel(
     pairs7(cXZ, p);
     S[SIXZ] = max7_packed<SIXZ, WRAP, true>(p, kp, two(sac), sh2);
   }
-  auto pk = [](int32_t lo, int32_t hi) { return (uint32_t)(uint16_t)lo | ((uint32_t)(uint16_t)hi << 16); };
-  *out = make_uint4(pk(S[0], S[1]), pk(S[2], S[3]), pk(S[4], S[5]), pk(S[6], 0));
-  if constexpr (TB) {  // one triple per traceback launch
-    uint32_t w = 0;
-#pragma unroll
-    for (int s = 0; s < NSTATE; ++s) w |= g[s] << (3 * s);
-    tb[tb_index(x, y, z, la, lc)] = w;
-  }
+  *out = pack7(S);
 
   if (x == la && y == lb && z == lc) {  // FINAL_MAX, src/TriAlign_1cyc.v:141-142
     int32_t m = S[0];
@@ -285,13 +226,12 @@ __global__ __launch_bounds__(64 * PLANE_TY) void plane_step_kernel(
   }
 }
 
-// Follow the pointers back from cell (la,lb,lc) (single thread; <= la+lb+lc
-// dependent loads). moves[] gets the states from the end backwards; info =
-// {moves, x0, y0, z0} where (x0,y0,z0) is the face cell the path leaves.
-__global__ void tb_walk(const uint32_t *__restrict__ tb, const int32_t *__restrict__ final7,
-                        int32_t la, int32_t lb, int32_t lc, uint8_t *__restrict__ moves,
-                        int32_t *__restrict__ info) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+// Follow the pointers back from cell (la,lb,lc) (<= la+lb+lc dependent
+// loads). moves[] gets the states from the end backwards; info = {moves, x0,
+// y0, z0} where (x0,y0,z0) is the face cell the path leaves.
+__device__ __forceinline__ void walk_back(const uint32_t *__restrict__ tb, const int32_t *__restrict__ final7,
+                                          int32_t la, int32_t lb, int32_t lc, uint8_t *__restrict__ moves,
+                                          int32_t *__restrict__ info) {
   // final MAX7 (src/TriAlign_1cyc.v:141-142): lowest state index on ties
   int32_t T = 0;
   for (int s = 1; s < NSTATE; ++s)
@@ -319,6 +259,36 @@ __global__ void tb_walk(const uint32_t *__restrict__ tb, const int32_t *__restri
   info[3] = z;
 }
 
+// The single-triple walk (one thread).
+__global__ void tb_walk(const uint32_t *__restrict__ tb, const int32_t *__restrict__ final7,
+                        int32_t la, int32_t lb, int32_t lc, uint8_t *__restrict__ moves,
+                        int32_t *__restrict__ info) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  walk_back(tb, final7, la, lb, lc, moves, info);
+}
+
+// The walks of n triples, one walker (thread) per triple: a walk is a chain of
+// dependent loads, so the triples are the parallelism. Triple t's cube starts
+// at word tb_off[t]; its moves go to moves[offs[3t] ..), in forward order (the
+// walker reverses its own slice), and its info to info[4t ..].
+__global__ __launch_bounds__(64) void tb_walk_batch(const uint32_t *__restrict__ tb,
+                                                    const int64_t *__restrict__ tb_off,
+                                                    const int64_t *__restrict__ offs, int32_t n,
+                                                    const int32_t *__restrict__ final7,
+                                                    uint8_t *__restrict__ moves, int32_t *__restrict__ info) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const int64_t o0 = offs[3 * t], o1 = offs[3 * t + 1], o2 = offs[3 * t + 2], o3 = offs[3 * t + 3];
+  uint8_t *mv = moves + o0;
+  walk_back(tb + tb_off[t], final7 + t * NSTATE, (int32_t)(o1 - o0), (int32_t)(o2 - o1), (int32_t)(o3 - o2), mv,
+            info + 4 * t);
+  for (int32_t i = 0, j = info[4 * t] - 1; i < j; ++i, --j) {
+    const uint8_t m = mv[i];
+    mv[i] = mv[j];
+    mv[j] = m;
+  }
+}
+
 size_t tb_cube_bytes(int32_t la, int32_t lb, int32_t lc) {
   return (size_t)lb * (size_t)(la + lc - 1) * (size_t)lc * sizeof(uint32_t);
 }
@@ -326,10 +296,10 @@ size_t tb_cube_bytes(int32_t la, int32_t lb, int32_t lc) {
 int plane_launch_batch(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n,
                        int32_t max_la, int32_t max_lb, int32_t max_lc, const KParams &kp,
                        int32_t *d_scores, int32_t *d_final7, void *d_ws, size_t ws_bytes,
-                       hipStream_t stream, uint32_t *d_tb) {
+                       hipStream_t stream, uint32_t *d_tb, const int64_t *d_tb_off) {
   if (n <= 0) return TSA_OK;
   if (n > 65535) return TSA_EINVAL;  // grid.z limit; callers chunk
-  if (d_tb && n != 1) return TSA_EINVAL;  // traceback: one triple, exact lengths
+  if (d_tb && n != 1 && !d_tb_off) return TSA_EINVAL;  // traceback of a batch: a cube offset per triple
   if (ws_bytes < plane_workspace_bytes(n, max_la, max_lb, max_lc)) return TSA_ENOMEM;
   const PlaneLayout L = plane_layout(max_lb, max_lc);
   uint4 *ws = (uint4 *)d_ws;
@@ -345,15 +315,23 @@ int plane_launch_batch(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t 
     const bool wrap = kp.bits > 0 && kp.bits < 16;
     if (d_tb)
       hipLaunchKernelGGL((plane_step_kernel<true, false>), grid, block, 0, stream, d_seqs, d_offsets,
-                         q, ws, L, kp, d_scores, d_final7, d_tb);
+                         q, ws, L, kp, d_scores, d_final7, d_tb, d_tb_off);
     else if (wrap)
       hipLaunchKernelGGL((plane_step_kernel<false, true>), grid, block, 0, stream, d_seqs, d_offsets,
-                         q, ws, L, kp, d_scores, d_final7, nullptr);
+                         q, ws, L, kp, d_scores, d_final7, nullptr, nullptr);
     else
       hipLaunchKernelGGL((plane_step_kernel<false, false>), grid, block, 0, stream, d_seqs, d_offsets,
-                         q, ws, L, kp, d_scores, d_final7, nullptr);
+                         q, ws, L, kp, d_scores, d_final7, nullptr, nullptr);
   }
   return hipGetLastError() == hipSuccess ? TSA_OK : TSA_EDEVICE;
+}
+
+int plane_launch_batch(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n,
+                       int32_t max_la, int32_t max_lb, int32_t max_lc, const KParams &kp,
+                       int32_t *d_scores, int32_t *d_final7, void *d_ws, size_t ws_bytes,
+                       hipStream_t stream, uint32_t *d_tb) {
+  return plane_launch_batch(d_seqs, d_offsets, n, max_la, max_lb, max_lc, kp, d_scores, d_final7, d_ws, ws_bytes,
+                            stream, d_tb, nullptr);
 }
 
 }  // namespace tsa

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "tsa_internal.h"
+#include "align_kernel.h"
 #include "pencil_kernel.h"
 #include "lap_kernel.h"
 
@@ -137,8 +138,9 @@ std::atomic<int64_t> g_kernel_launches{0};
 
 // ---- plan overrides (tsa_set_override) --------------------------------------
 namespace {
-const char *const kOverrideNames[] = {"lap_chunk", "lap_m",       "lap_nw",       "lap_spin_limit", "lap_trace",
-                                      "lap_vs",    "pencil_arith", "pencil_mode", "pencil_two",     "split_serial"};
+const char *const kOverrideNames[] = {"align_mode", "align_tb_bytes", "lap_chunk",    "lap_m",
+                                      "lap_nw",     "lap_spin_limit", "lap_trace",    "lap_vs",
+                                      "pencil_arith", "pencil_mode",  "pencil_two",   "split_serial"};
 constexpr int kNOverrides = (int)(sizeof(kOverrideNames) / sizeof(kOverrideNames[0]));
 constexpr size_t kOverrideMax = 256;
 std::mutex ov_mu;
@@ -873,6 +875,189 @@ done:
   if (d_tb) (void)hipFree(d_tb);
   if (s) (void)hipStreamDestroy(s);
   return rc;
+}
+
+}  // extern "C"
+
+namespace {
+// Device buffers and the stream of one tsa_align_batch call, released on every
+// exit path.
+struct AlignBufs {
+  std::vector<void *> ptrs;
+  hipStream_t s = nullptr;
+  template <class T>
+  bool alloc(T **p, size_t bytes) {
+    void *v = nullptr;
+    if (hipMalloc(&v, std::max<size_t>(bytes, 16)) != hipSuccess) return false;
+    ptrs.push_back(v);
+    *p = (T *)v;
+    return true;
+  }
+  ~AlignBufs() {
+    for (void *v : ptrs) (void)hipFree(v);
+    if (s) (void)hipStreamDestroy(s);
+  }
+};
+}  // namespace
+
+extern "C" {
+
+// Which path a triple takes: the resident kernel (one launch per chunk) when
+// its planes fit a workgroup, the batched plane sweep when not. On the MI355X
+// the resident kernel was the faster of the two on every recorded shape it
+// holds (profiles/align_batch.jsonl: 512 x 64^3 and 64 x 64^3 related triples),
+// so a fitting triple is resident unless align_mode = plane says otherwise.
+static bool align_takes_resident(bool force_plane, int32_t la, int32_t lb, int32_t lc) {
+  return !force_plane && align_resident_fits(la, lb, lc);
+}
+
+int tsa_align_batch(const uint8_t *seqs, const int64_t *offsets, int32_t n, const tsa_params *p,
+                    int32_t *scores, uint8_t *moves, int32_t *n_moves, int32_t *starts, int32_t device) {
+  if (!seqs || !offsets || !scores || !moves || !n_moves || !starts || n < 0 || !params_ok(p)) return TSA_EINVAL;
+  for (int32_t i = 0; i < n; ++i) {
+    const int64_t *o = offsets + 3 * (int64_t)i;
+    if (o[1] < o[0] || o[2] < o[1] || o[3] < o[2]) return TSA_EINVAL;
+    int rc = tsa_validate(seqs + o[0], (int32_t)(o[1] - o[0]), seqs + o[1], (int32_t)(o[2] - o[1]),
+                          seqs + o[2], (int32_t)(o[3] - o[2]), p);
+    if (rc) return rc;
+  }
+  if (n == 0) return TSA_OK;
+  const int nd = tsa_device_count();
+  if (nd <= 0) return TSA_ENODEV;
+  if (device < 0 || device >= nd) return TSA_ENODEV;
+  KParams kp;
+  int rc = build_kparams(p, &kp);
+  if (rc) return rc;
+  char mode[32];
+  bool force_plane = false;
+  if (override_str("align_mode", mode, sizeof mode)) {
+    if (!strcmp(mode, "plane")) force_plane = true;
+    else if (strcmp(mode, "resident")) return TSA_EINVAL;
+  }
+  AlignBufs B;
+  if (hipSetDevice(device) != hipSuccess) return TSA_EDEVICE;
+  // The pointer-cube budget of a chunk: align_tb_bytes, or half of the device
+  // memory free at the call (the other half is left to the caller's own
+  // buffers and to the sequences, moves and plane rings of the chunk, all of
+  // which are O(N^2) against the cubes' O(N^3)).
+  size_t budget = 0;
+  long ov = 0;
+  if (override_int("align_tb_bytes", &ov)) {
+    if (ov < 0) return TSA_EINVAL;
+    budget = (size_t)ov;
+  } else {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return TSA_EDEVICE;
+    budget = free_b / 2;
+  }
+  auto len_of = [&](int32_t i, int k) { return (int32_t)(offsets[3 * (int64_t)i + k + 1] - offsets[3 * (int64_t)i + k]); };
+  // chunks of consecutive triples whose cubes fit the budget together
+  std::vector<int32_t> chunk_end;
+  size_t max_cube = 0, max_seq = 0, max_ws = 0;
+  int32_t max_n = 0;
+  for (int32_t i = 0; i < n;) {
+    size_t cube = 0, seq = 0;
+    int32_t j = i, mla = 1, mlb = 1, mlc = 1, np = 0;
+    for (; j < n && j - i < 65535; ++j) {
+      const int32_t la = len_of(j, 0), lb = len_of(j, 1), lc = len_of(j, 2);
+      const size_t c = tb_cube_bytes(la, lb, lc);
+      if (c > budget) return TSA_ENOMEM;  // one cube over the budget, as tsa_align_gpu's failed allocation
+      if (cube + c > budget) break;
+      cube += c;
+      seq += (size_t)la + lb + lc;
+      if (!align_takes_resident(force_plane, la, lb, lc)) {
+        mla = std::max(mla, la), mlb = std::max(mlb, lb), mlc = std::max(mlc, lc);
+        ++np;
+      }
+    }
+    chunk_end.push_back(j);
+    max_cube = std::max(max_cube, cube);
+    max_seq = std::max(max_seq, seq);
+    max_n = std::max(max_n, j - i);
+    if (np) max_ws = std::max(max_ws, plane_workspace_bytes(np, mla, mlb, mlc));
+    i = j;
+  }
+  // device buffers, once per call, sized for the largest chunk
+  uint8_t *d_seqs = nullptr, *d_moves = nullptr;
+  int64_t *d_meta = nullptr;  // [0, 3m] offsets, then m cube word offsets
+  int32_t *d_res = nullptr;   // m scores, 7m final states, 4m walk infos
+  uint32_t *d_tb = nullptr;
+  void *d_ws = nullptr;
+  if (hipStreamCreateWithFlags(&B.s, hipStreamNonBlocking) != hipSuccess) return TSA_EDEVICE;
+  if (!B.alloc(&d_seqs, max_seq) || !B.alloc(&d_moves, max_seq) ||
+      !B.alloc(&d_meta, sizeof(int64_t) * (4 * (size_t)max_n + 1)) ||
+      !B.alloc(&d_res, sizeof(int32_t) * 12 * (size_t)max_n) || !B.alloc(&d_tb, max_cube) ||
+      !B.alloc(&d_ws, max_ws))
+    return TSA_ENOMEM;
+  std::vector<uint8_t> h_seqs(max_seq), h_moves(max_seq);
+  std::vector<int64_t> h_meta(4 * (size_t)max_n + 1);
+  std::vector<int32_t> h_res(12 * (size_t)max_n), order((size_t)max_n);
+  int32_t i0 = 0;
+  for (const int32_t i1 : chunk_end) {
+    // the chunk as a batch of its own: resident triples first, then the plane
+    // path's, packed back to back, so each path sees a contiguous sub-batch
+    const int32_t m = i1 - i0;
+    int32_t mr = 0;
+    for (int32_t i = i0; i < i1; ++i)
+      if (align_takes_resident(force_plane, len_of(i, 0), len_of(i, 1), len_of(i, 2))) order[mr++] = i;
+    int32_t k = mr;
+    for (int32_t i = i0; i < i1; ++i)
+      if (!align_takes_resident(force_plane, len_of(i, 0), len_of(i, 1), len_of(i, 2))) order[k++] = i;
+    int64_t pos = 0, word = 0, max_pos = 1;
+    size_t lds = 0;
+    int32_t mla = 1, mlb = 1, mlc = 1;
+    int64_t *h_off = h_meta.data(), *h_tboff = h_meta.data() + 3 * (size_t)m + 1;
+    for (int32_t j = 0; j < m; ++j) {
+      const int32_t i = order[j], la = len_of(i, 0), lb = len_of(i, 1), lc = len_of(i, 2);
+      std::memcpy(h_seqs.data() + pos, seqs + offsets[3 * (int64_t)i], (size_t)la + lb + lc);
+      h_off[3 * j] = pos, h_off[3 * j + 1] = pos + la, h_off[3 * j + 2] = pos + la + lb;
+      pos += (int64_t)la + lb + lc;
+      h_tboff[j] = word;
+      word += (int64_t)(tb_cube_bytes(la, lb, lc) / sizeof(uint32_t));
+      if (j < mr) {
+        max_pos = std::max<int64_t>(max_pos, (int64_t)lb * lc);
+        lds = std::max(lds, align_resident_lds(la, lb, lc));
+      } else {
+        mla = std::max(mla, la), mlb = std::max(mlb, lb), mlc = std::max(mlc, lc);
+      }
+    }
+    h_off[3 * m] = pos;
+    int32_t *d_scores = d_res, *d_final7 = d_res + m, *d_info = d_res + 8 * (size_t)m;
+    const int64_t *d_off = d_meta, *d_tboff = d_meta + 3 * (size_t)m + 1;
+    if (hipMemcpyAsync(d_seqs, h_seqs.data(), (size_t)pos, hipMemcpyHostToDevice, B.s) != hipSuccess ||
+        hipMemcpyAsync(d_meta, h_meta.data(), sizeof(int64_t) * (4 * (size_t)m + 1), hipMemcpyHostToDevice, B.s) !=
+            hipSuccess)
+      return TSA_EDEVICE;
+    if (mr && (rc = align_launch_resident(d_seqs, d_off, mr, max_pos, lds, kp, d_scores, d_final7, d_tb, d_tboff, B.s)))
+      return rc;
+    if (m > mr) {
+      const int32_t mp = m - mr;
+      const size_t ws_bytes = plane_workspace_bytes(mp, mla, mlb, mlc);
+      if ((rc = plane_launch_batch(d_seqs, d_off + 3 * (size_t)mr, mp, mla, mlb, mlc, kp, d_scores + mr,
+                                   d_final7 + (size_t)NSTATE * mr, d_ws, ws_bytes, B.s, d_tb, d_tboff + mr)))
+        return rc;
+    }
+    hipLaunchKernelGGL(tb_walk_batch, dim3((m + 63) / 64), dim3(64), 0, B.s, d_tb, d_tboff, d_off, m, d_final7, d_moves,
+                       d_info);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(h_res.data(), d_res, sizeof(int32_t) * 12 * (size_t)m, hipMemcpyDeviceToHost, B.s) !=
+            hipSuccess ||
+        hipMemcpyAsync(h_moves.data(), d_moves, (size_t)pos, hipMemcpyDeviceToHost, B.s) != hipSuccess ||
+        hipStreamSynchronize(B.s) != hipSuccess)
+      return TSA_EDEVICE;
+    for (int32_t j = 0; j < m; ++j) {
+      const int32_t i = order[j];
+      const int32_t *info = h_res.data() + 8 * (size_t)m + 4 * (size_t)j;
+      const int64_t len = offsets[3 * (int64_t)i + 3] - offsets[3 * (int64_t)i];
+      if (info[0] < 1 || info[0] > len) return TSA_EINTERNAL;
+      std::memcpy(moves + (offsets[3 * (int64_t)i] - offsets[0]), h_moves.data() + h_off[3 * j], (size_t)info[0]);
+      scores[i] = h_res[j];
+      n_moves[i] = info[0];
+      starts[3 * (int64_t)i] = info[1], starts[3 * (int64_t)i + 1] = info[2], starts[3 * (int64_t)i + 2] = info[3];
+    }
+    i0 = i1;
+  }
+  return TSA_OK;
 }
 
 // tsa_describe_plan's suffix while plan overrides are set: " overrides=..."

@@ -230,6 +230,34 @@ int tsa_align_gpu(const uint8_t *a, int32_t la, const uint8_t *b, int32_t lb,
                   uint8_t *moves, int32_t max_moves, int32_t *n_moves, int32_t *start,
                   int32_t device);
 
+/* Optimal alignments of a batch of triples (synchronous, HIP device `device`):
+ * tsa_align_gpu for n triples in one call. seqs and offsets (3n+1 of them) are
+ * laid out as for tsa_score_batch; lengths may differ from triple to triple.
+ * moves has the layout of seqs: triple i owns
+ *   moves[offsets[3i] - offsets[0] .. offsets[3i+3] - offsets[0])
+ * (la+lb+lc bytes), whose first n_moves[i] bytes receive its columns in
+ * forward order (TSA_MOVE_*); starts[3i..3i+2] is the face cell its path
+ * leaves and scores[i] its score. Per triple the result is that of
+ * tsa_align_gpu: literal wrapped arithmetic for every parameter set, lowest
+ * state index on ties, free start at the zero faces. Thread-safe; retains no
+ * caller pointer. Validation comes before any device work: TSA_EINVAL (or
+ * tsa_validate's code) for null pointers, n < 0, non-monotone offsets, bad
+ * symbols or parameters; TSA_OK for n == 0; TSA_ENODEV with no HIP device
+ * (there is no CPU fallback).
+ * A triple whose (y,z) planes fit one workgroup (lb*lc <= 4096 and
+ * 32*(lb+1)*(lc+1) + lb + lc bytes within the 160 KiB of LDS; 64 x 64 fits,
+ * LA is unbounded) is swept by the resident kernel, one launch for all such
+ * triples of a chunk; the others run the plane sweep, one launch per plane for
+ * all of them (override align_mode). The pointer cubes cost 4*lb*(la+lc-1)*lc
+ * bytes per triple: the batch is processed in chunks of consecutive triples
+ * whose cubes fit a budget -- half of the device memory free at the call, or
+ * the override align_tb_bytes -- and a triple whose own cube exceeds the
+ * budget is TSA_ENOMEM, as is a failed device allocation. No RTL counterpart
+ * (see tsa_align_gpu). */
+int tsa_align_batch(const uint8_t *seqs, const int64_t *offsets, int32_t n,
+                    const tsa_params *p, int32_t *scores, uint8_t *moves,
+                    int32_t *n_moves, int32_t *starts, int32_t device);
+
 /* Which kernel, arithmetic and schedule a batch of these sizes would run, as a
  * short text such as "pencil lap f16 rtl M=1 NW=16 laps=16 tiles=1 waves=1"
  * or "plane" (sync = 1: the synchronous tsa_score_batch path, which may stream
@@ -250,9 +278,11 @@ int64_t tsa_fallback_count(void);
  * (TSA_KERNEL_PLANE's plan). */
 int64_t tsa_check_fallback_count(void);
 
-/* Scoring-kernel launches (helix, lap, literal helix) the library has queued
+/* Kernel launches with dynamic LDS (helix, lap, literal helix; the resident
+ * traceback kernel of tsa_align_batch, one per chunk) the library has queued
  * since it was loaded: a call that reuses an error left over from an earlier
- * HIP call must still launch its kernel exactly once (tests). */
+ * HIP call must still launch its kernel exactly once (tests). The plane sweep
+ * and the traceback walks are not counted. */
 int64_t tsa_kernel_launch_count(void);
 
 /* Number of visible HIP devices (0 when none), or a negative code. */
@@ -283,6 +313,9 @@ const char *tsa_version(void);
  *   lap_spin_limit  polls before a lap hand-off times out (0: at once)
  *   lap_trace       path of a per-workgroup timestamp CSV (tools/lap_trace.py)
  *   split_serial    0 | 1           (tsa_score_gpu_multi parts one by one)
+ *   align_mode      resident | plane (tsa_align_batch: resident still sends a
+ *                   triple that does not fit a workgroup to the plane sweep)
+ *   align_tb_bytes  pointer-cube budget of a tsa_align_batch chunk, in bytes
  * value NULL clears `name`; name NULL clears every override. TSA_EINVAL for an
  * unknown name or a value longer than 255 bytes. The reference has no
  * counterpart: its datapath parameters are fixed at build (src/PE_1cyc.v:55-61). */

@@ -1,0 +1,90 @@
+#!/usr/bin/env python3
+"""Wall time of batched traceback: tsa_align_batch under align_mode=resident
+and align_mode=plane, and a loop of tsa_align_gpu over the same triples, in
+ONE process with the passes interleaved (every pass runs each form once, in
+turn), after warm-up passes that are not timed. All three calls are
+synchronous, so host wall time is the time a caller waits.
+  python tools/align_bench.py --n 512 --la 64 --lb 64 --lc 64
+  python tools/align_bench.py --n 64 --la 64 --related
+A library without tsa_align_batch (an older build named by TSA_PKG_DIR) runs
+the loop alone: that is how the baseline of a comparison is taken.
+Prints one JSON line: per form the median, min and max of the passes in ms."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=512)
+    ap.add_argument("--la", type=int, default=64)
+    ap.add_argument("--lb", type=int, default=None)
+    ap.add_argument("--lc", type=int, default=None)
+    ap.add_argument("--related", action="store_true", help="related triples (B, C = mutated A), cubes only")
+    ap.add_argument("--passes", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--loop-n", type=int, default=None, help="triples of the align loop (default: all)")
+    ap.add_argument("--forms", default="resident,plane,loop")
+    args = ap.parse_args()
+    import bench
+    tsa = bench.load_pkg()
+    import tsa_amd.synth as synth
+    la = args.la
+    lb = la if args.lb is None else args.lb
+    lc = la if args.lc is None else args.lc
+    if args.related:
+        trips = [synth.related_triple(900 + i, la) for i in range(args.n)]
+        lb = lc = la
+    else:
+        trips = [synth.triple(i, la, lb, lc) for i in range(args.n)]
+    seqs, offs = tsa.pack_batch(trips)
+    loop_n = args.n if args.loop_n is None else min(args.loop_n, args.n)
+    have_batch = hasattr(tsa, "align_batch")
+
+    def batch(mode):
+        def run():
+            with tsa.overrides(align_mode=mode):
+                return tsa.align_batch(seqs=seqs, offsets=offs)
+        return run
+
+    def loop():
+        return [tsa.align(a, b, c) for a, b, c in trips[:loop_n]]
+
+    forms = {}
+    for f in args.forms.split(","):
+        if f == "loop":
+            forms[f] = loop
+        elif have_batch:
+            forms[f] = batch(f)
+    out = {f: fn() for f, fn in forms.items()}       # first call: also the cross-check
+    names = list(out)
+    same = True
+    for f in names[1:]:
+        for g, r in zip(out[f], out[names[0]]):
+            same = same and g[0] == r[0] and tuple(g[1]) == tuple(r[1]) and bool((g[2] == r[2]).all())
+    times = {f: [] for f in forms}
+    for k in range(args.warmup + args.passes):
+        for f, fn in forms.items():
+            t0 = time.perf_counter()
+            fn()
+            dt = (time.perf_counter() - t0) * 1e3
+            if k >= args.warmup:
+                times[f].append(dt)
+    res = {"bench": "align", "n": args.n, "shape": [la, lb, lc], "related": bool(args.related),
+           "passes": args.passes, "warmup": args.warmup, "loop_n": loop_n, "forms_agree": same,
+           "version": tsa.version()}
+    for f, ts in times.items():
+        scale = args.n / loop_n if f == "loop" else 1.0  # a shortened loop, scaled to the batch
+        res[f + "_ms"] = {"median": round(statistics.median(ts) * scale, 3), "min": round(min(ts) * scale, 3),
+                          "max": round(max(ts) * scale, 3)}
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
