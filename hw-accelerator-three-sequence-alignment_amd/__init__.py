@@ -64,12 +64,12 @@ EXPORTS = (
     "tsa_device_count", "tsa_strerror", "tsa_version", "tsa_describe_plan", "tsa_align_gpu",
     "tsa_fallback_count", "tsa_check_fallback_count", "tsa_score_batch_async_p2", "tsa_pack2",
     "tsa_score_gpu_multi", "tsa_score_batch_devices", "tsa_set_override", "tsa_get_overrides",
-    "tsa_kernel_launch_count", "tsa_align_batch",
+    "tsa_kernel_launch_count", "tsa_align_batch", "tsa_describe_align_plan",
 )
 
 # Plan overrides the library accepts (tsa_set_override; include/trialign.h).
-OVERRIDES = ("align_mode", "align_tb_bytes", "lap_chunk", "lap_m", "lap_nw", "lap_spin_limit", "lap_trace", "lap_vs",
-             "pencil_arith", "pencil_mode", "pencil_two", "split_serial")
+OVERRIDES = ("align_mode", "align_tb_bytes", "align_tile", "lap_chunk", "lap_m", "lap_nw", "lap_spin_limit", "lap_trace",
+             "lap_vs", "pencil_arith", "pencil_mode", "pencil_two", "split_serial")
 
 # Score of a triple the device could not score (include/trialign.h).
 SCORE_INVALID = -(2 ** 31)
@@ -142,6 +142,7 @@ def _load_lib() -> ctypes.CDLL:
                                           ctypes.c_size_t, ctypes.c_void_p]
     lib.tsa_describe_plan.argtypes = [ctypes.c_int32] * 4 + [pp, ctypes.c_int32, ctypes.c_int32,
                                                             ctypes.c_char_p, ctypes.c_size_t]
+    lib.tsa_describe_align_plan.argtypes = [ctypes.c_int32] * 4 + [pp, ctypes.c_char_p, ctypes.c_size_t]
     lib.tsa_align_gpu.argtypes = [u8p, ctypes.c_int32, u8p, ctypes.c_int32, u8p, ctypes.c_int32,
                                   pp, i32p, u8p, ctypes.c_int32, i32p, i32p, ctypes.c_int32]
     lib.tsa_align_batch.argtypes = [u8p, i64p, ctypes.c_int32, pp, i32p, u8p, i32p, i32p,
@@ -168,7 +169,7 @@ def _load_lib() -> ctypes.CDLL:
                  "tsa_batch_workspace_size", "tsa_score_batch_async", "tsa_device_count",
                  "tsa_describe_plan", "tsa_align_gpu", "tsa_score_batch_async_p2", "tsa_pack2",
                  "tsa_score_gpu_multi", "tsa_score_batch_devices", "tsa_set_override",
-                 "tsa_get_overrides", "tsa_align_batch"):
+                 "tsa_get_overrides", "tsa_align_batch", "tsa_describe_align_plan"):
         getattr(lib, name).restype = ctypes.c_int
     return lib
 
@@ -250,8 +251,9 @@ class overrides:
 
 
 def kernel_launch_count() -> int:
-    """Scoring-kernel launches (and resident traceback launches, one per
-    align_batch chunk) queued since the library was loaded."""
+    """Scoring-kernel launches (and resident / tiled resident traceback
+    launches, one each per align_batch chunk) queued since the library was
+    loaded."""
     return int(_lib.tsa_kernel_launch_count())
 
 
@@ -369,8 +371,10 @@ def align_batch(triples=None, params: Optional[TsaParams] = None, device: int = 
     """Optimal alignments of many triples in one call (tsa_align_batch): a
     list of ``(score, start, moves)``, one per triple in the caller's order,
     each as ``align`` returns it. Triples whose (y,z) planes fit a workgroup
-    run the resident kernel, one launch per chunk of pointer cubes; the
-    overrides ``align_mode`` and ``align_tb_bytes`` steer path and chunking."""
+    run the resident kernel, one launch per chunk of pointer cubes; larger
+    ones the plane sweep or, under ``align_mode="tiled"``, the tiled resident
+    kernel (``describe_align_plan``). The overrides ``align_mode``,
+    ``align_tile`` and ``align_tb_bytes`` steer path, tiling and chunking."""
     p = params or TsaParams.default()
     if seqs is None:
         seqs, offsets = pack_batch(triples)
@@ -527,6 +531,17 @@ def describe_plan(n: int, max_la: int, max_lb: int, max_lc: int,
     buf = ctypes.create_string_buffer(512)
     _check(_lib.tsa_describe_plan(n, max_la, max_lb, max_lc, ctypes.byref(p), k, int(sync), buf,
                                   len(buf)), "tsa_describe_plan")
+    return buf.value.decode()
+
+
+def describe_align_plan(n: int, la: int, lb: int, lc: int, params: Optional[TsaParams] = None) -> str:
+    """The path a group of ``n`` triples of these lengths takes in
+    ``align_batch`` under the current overrides (tsa_describe_align_plan;
+    host-only): ``resident ...``, ``tiled tile=TYxTZ tiles=NYxNZ ...`` or
+    ``plane``."""
+    p = params or TsaParams.default()
+    buf = ctypes.create_string_buffer(256)
+    _check(_lib.tsa_describe_align_plan(n, la, lb, lc, ctypes.byref(p), buf, len(buf)), "tsa_describe_align_plan")
     return buf.value.decode()
 
 

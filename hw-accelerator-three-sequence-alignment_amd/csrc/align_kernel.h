@@ -36,4 +36,38 @@ int align_launch_resident(const uint8_t *d_seqs, const int64_t *d_offsets, int32
                           const KParams &kp, int32_t *d_scores, int32_t *d_final7, uint32_t *d_tb,
                           const int64_t *d_tb_off, hipStream_t stream);
 
+// The tiled resident kernel (align_tiled_kernel.hip): one workgroup sweeps a
+// cube whose (y,z) plane does not fit it, tile by tile, the tiles chained
+// through face buffers in global memory. Balanced tiles under the caps
+// tymax x tzmax (align_tile_fits): nty = ceil(lb/tymax) tiles of
+// TY = ceil(lb/nty) rows (the last one shorter, never empty), likewise along z.
+struct AlignTileGeom {
+  int32_t TY, TZ, nty, ntz;
+};
+__host__ __device__ inline AlignTileGeom align_tile_geom(int32_t lb, int32_t lc, int32_t tymax, int32_t tzmax) {
+  AlignTileGeom g;
+  g.nty = (lb + tymax - 1) / tymax;
+  g.ntz = (lc + tzmax - 1) / tzmax;
+  g.TY = (lb + g.nty - 1) / g.nty;
+  g.TZ = (lc + g.ntz - 1) / g.ntz;
+  return g;
+}
+// A tile the tiled kernel can sweep: within the resident capacity
+// (align_resident_fits) and within 3 positions per thread of a 1024-thread
+// workgroup -- the fourth position the resident kernel has would spill here.
+bool align_tile_fits(int32_t ty, int32_t tz);
+// The default tile caps: 3072 positions, a row of B symbols as deep as the
+// resident kernel's.
+constexpr int32_t ALIGN_TILE_Y = 64, ALIGN_TILE_Z = 48;
+// 16-byte cells of a triple's face workspace: two y faces [la][lc+1] and two
+// z faces [la][TY].
+size_t align_tiled_face_cells(int32_t la, int32_t lb, int32_t lc, int32_t tymax, int32_t tzmax);
+// One launch for n triples through launch_with_lds: max_pos = the largest
+// TY*TZ and lds = the largest align_resident_lds(la, TY, TZ) of the batch;
+// d_face_off[t] = the cell offset of triple t's face workspace in d_faces.
+int align_launch_tiled(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, int32_t tymax, int32_t tzmax,
+                       int64_t max_pos, size_t lds, const KParams &kp, int32_t *d_scores, int32_t *d_final7,
+                       uint32_t *d_tb, const int64_t *d_tb_off, void *d_faces, const int64_t *d_face_off,
+                       hipStream_t stream);
+
 }  // namespace tsa

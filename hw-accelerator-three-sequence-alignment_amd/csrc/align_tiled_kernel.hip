@@ -1,0 +1,237 @@
+// align_tiled_kernel.hip -- the tiled resident traceback kernel of
+// tsa_align_batch: one workgroup sweeps a whole (la,lb,lc) cube whose (y,z)
+// plane is larger than a workgroup holds, tile by tile, in one launch.
+//
+// Reference: a (y,z) plane larger than the PE array is sliced into pencils
+// swept one after another and chained through face SRAMs
+// (src/TriAlign_1cyc.v:78-98,127-140); the cell is that of align_kernel.hip
+// (src/PE_1cyc.v:159-218, MAX7 src/PE_1cyc.v:1-32, final MAX7
+// src/TriAlign_1cyc.v:141-142), literal_cell.h's max7_literal on the same
+// operands. Traceback itself is an extension (src/TriAlign_tb.sv:239-260).
+//
+// Schedule (tools/align_tiled_emu.py replays it on the CPU). The plane is cut
+// into nty x ntz balanced tiles of at most TY x TZ positions
+// (align_tile_geom); the workgroup of a triple sweeps them ty outer, tz inner,
+// so tiles (ty-1,tz), (ty,tz-1) and (ty-1,tz-1) are finished when (ty,tz)
+// starts. A tile is swept over all x by the resident schedule of
+// align_kernel.hip in local coordinates: step q, local position (y,z) at
+// x = q-y-z, two zeroed LDS buffers of 16-byte cells with a row 0 and a column
+// 0, publication only while 1 <= x <= la, the 5-state register history, one
+// barrier per step. What differs is what row 0 and column 0 hold. In the first
+// tile row / column they are the zero faces and nothing is published. In every
+// other tile the face position (0,z) is at x = q-z, (y,0) at x = q-y and the
+// corner (0,0) at x = q, and while 1 <= x <= la it publishes into buf[q&1] the
+// cell the neighbouring tile stored for that (x, global y, global z): the
+// rule a real position follows, with a load in place of the cell. (The corner
+// publishes x = 1 at step 1, one step before the first real read.) The packed
+// cell of a position of a tile's last local row goes into the y face
+// [x][global z], that of the last local column into the z face [x][local y];
+// the face threads copy it from buf[(q-1)&1] one step after it was published,
+// so the cell's own registers carry no face work.
+// The y face alternates between two buffers by the parity of ty -- tile
+// (ty,tz+1) reads its corner, global z0 of row ty-1, after (ty,tz) has
+// written row ty -- and the z face by the parity of tz. Both LDS buffers are
+// zeroed and the history reset at the start of every tile, so no cell of the
+// last tile reads as a face and the x = 0 face is zero for every tile.
+//
+// Ordering: face stores and face loads are plain global accesses by threads of
+// one workgroup, a tile apart, so at least the end-of-tile __syncthreads()
+// lies between them (workgroup scope on one CU). No workgroup waits for
+// another: there is no flag, fence or poll.
+
+#include "align_kernel.h"
+#include "literal_cell.h"
+#include "pencil_common.h"
+
+namespace tsa {
+
+constexpr int TILED_NT = 1024;  // threads of a workgroup at most
+constexpr int TILED_K = 3;      // positions per thread at most: 126 VGPRs of the 128; a fourth would spill
+
+bool align_tile_fits(int32_t ty, int32_t tz) {
+  return ty >= 1 && tz >= 1 && (int64_t)ty * tz <= (int64_t)TILED_NT * TILED_K && align_resident_fits(1, ty, tz);
+}
+
+size_t align_tiled_face_cells(int32_t la, int32_t lb, int32_t lc, int32_t tymax, int32_t tzmax) {
+  const AlignTileGeom g = align_tile_geom(lb, lc, tymax, tzmax);
+  return 2 * (size_t)la * ((size_t)lc + 1) + 2 * (size_t)la * (size_t)g.TY;
+}
+
+template <int K>
+__global__ __launch_bounds__(TILED_NT) void align_tiled_kernel(
+    const uint8_t *__restrict__ seqs, const int64_t *__restrict__ offs, KParams kp, uint32_t lds_bytes,
+    int32_t tymax, int32_t tzmax, int32_t *__restrict__ scores, int32_t *__restrict__ final7,
+    uint32_t *__restrict__ tb, const int64_t *__restrict__ tb_off, uint4 *faces,
+    const int64_t *__restrict__ face_off) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const int64_t t = blockIdx.x;
+  const int64_t o0 = offs[3 * t], o1 = offs[3 * t + 1], o2 = offs[3 * t + 2], o3 = offs[3 * t + 3];
+  const int32_t la = (int32_t)(o1 - o0), lb = (int32_t)(o2 - o1), lc = (int32_t)(o3 - o2);
+  const AlignTileGeom tg = align_tile_geom(lb, lc, tymax, tzmax);
+  const int32_t TY = tg.TY, TZ = tg.TZ;
+  const int32_t ldz = TZ + 1, ncell = (TY + 1) * ldz;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  uint4 *buf0 = (uint4 *)smem, *buf1 = buf0 + ncell;
+  uint8_t *sym = (uint8_t *)(buf1 + ncell);
+  // A staged only when the launch's LDS has room for it
+  const bool a_lds = 2 * sizeof(uint4) * (size_t)ncell + (size_t)TY + TZ + la <= lds_bytes;
+  uint8_t *sB = sym, *sC = sym + TY;
+  const uint8_t *sA = sym + TY + TZ;
+  if (a_lds)
+    for (int32_t i = tid; i < la; i += nt) sym[TY + TZ + i] = (uint8_t)tsa_sym(seqs, o0 + i, kp.packed);
+  // the face workspace of this triple: y faces [2][la][lc+1], z faces [2][la][TY]
+  const int64_t ysz = (int64_t)la * (lc + 1), zsz = (int64_t)la * TY;
+  uint4 *yf = faces + face_off[t], *zf = yf + 2 * ysz;
+  uint32_t *cube = tb + tb_off[t];
+  const int32_t sh = kp.wrap_shift;
+  auto symA = [&](int32_t i) {  // a_{i+1}, the index clamped into the sequence
+    i = min(max(i, 0), la - 1);
+    return a_lds ? (int)sA[i] : (int)tsa_sym(seqs, o0 + i, kp.packed);
+  };
+  for (int32_t ty = 0; ty < tg.nty; ++ty)
+    for (int32_t tz = 0; tz < tg.ntz; ++tz) {
+      const int32_t y0 = ty * TY, z0 = tz * TZ;
+      const int32_t tyl = min(TY, lb - y0), tzl = min(TZ, lc - z0);
+      // the last step's barrier of the tile before lies behind: zero both
+      // buffers again and stage the tile's symbols of B and C
+      for (int32_t i = tid; i < 2 * ncell; i += nt) buf0[i] = make_uint4(0u, 0u, 0u, 0u);
+      for (int32_t i = tid; i < tyl; i += nt) sB[i] = (uint8_t)tsa_sym(seqs, o1 + y0 + i, kp.packed);
+      for (int32_t i = tid; i < tzl; i += nt) sC[i] = (uint8_t)tsa_sym(seqs, o2 + z0 + i, kp.packed);
+      __syncthreads();
+      // faces this tile reads (null: the zero face) and writes (null: no tile beyond)
+      const uint4 *yrd = ty ? yf + ((ty - 1) & 1) * ysz : nullptr;
+      const uint4 *zrd = tz ? zf + ((tz - 1) & 1) * zsz : nullptr;
+      uint4 *ywr = ty + 1 < tg.nty ? yf + (ty & 1) * ysz : nullptr;
+      uint4 *zwr = tz + 1 < tg.ntz ? zf + (tz & 1) * zsz : nullptr;
+      // position k of this thread: y | z << 13 | b << 26 | c << 28 | valid << 30 (local y, z)
+      uint32_t meta[K], gh[K];                         // gh: the 5 kept argmaxes, 3 bits each
+      int32_t hXY[K], hYZ[K], hXZ[K], hM3[K], hM2[K];  // the kept states
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const int32_t p = k * nt + tid;
+        meta[k] = 0;
+        if (p < tyl * tzl) {
+          const int32_t y = p / tzl + 1, z = p % tzl + 1;
+          meta[k] = (uint32_t)y | ((uint32_t)z << 13) | ((uint32_t)sB[y - 1] << 26) | ((uint32_t)sC[z - 1] << 28) |
+                    (1u << 30);
+        }
+        gh[k] = 0;
+        hXY[k] = hYZ[k] = hXZ[k] = hM3[k] = hM2[k] = 0;
+      }
+      const int32_t qmax = la + tyl + tzl + ((ywr || zwr) ? 1 : 0);
+      for (int32_t q = 1; q <= qmax; ++q) {
+        const uint4 *rd = (q & 1) ? buf0 : buf1;  // buf[(q-1)&1]
+        uint4 *wr = (q & 1) ? buf1 : buf0;        // buf[q&1]
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          const int32_t y = (int32_t)(meta[k] & 0x1FFFu), z = (int32_t)((meta[k] >> 13) & 0x1FFFu);
+          const int32_t x = q - y - z;
+          if ((meta[k] >> 30) && x >= 0 && x <= la) {
+            const int32_t idx = y * ldz + z;
+            const int b = (int)((meta[k] >> 26) & 3u), cc = (int)((meta[k] >> 28) & 3u);
+            int32_t pr[7], sab, sbc, sac, s3;
+            uint32_t g;
+            if (x == 0) {  // M of x = 1 comes from the corner of the zero x = 0 face
+              const int32_t zero7[7] = {0, 0, 0, 0, 0, 0, 0};
+              literal_adds(kp, symA(0), b, cc, sh, sab, sbc, sac, s3);
+              hM3[k] = max7_literal<SM, true>(zero7, kp, s3, sh, g);
+              gh[k] = (gh[k] & ~(7u << 9)) | (g << 9);
+            } else {
+              int32_t S[7];
+              uint32_t w = (gh[k] & 7u) << (3 * SIXY) | ((gh[k] >> 3) & 7u) << (3 * SIYZ) |
+                           ((gh[k] >> 6) & 7u) << (3 * SIXZ) | ((gh[k] >> 9) & 7u) << (3 * SM);
+              S[SM] = hM3[k];
+              S[SIXY] = hXY[k];
+              S[SIYZ] = hYZ[k];
+              S[SIXZ] = hXZ[k];
+              unpack7(rd[idx], pr);  // own: (x-1, y, z)
+              S[SIX] = max7_literal<SIX, true>(pr, kp, 0, sh, g);
+              w |= g << (3 * SIX);
+              unpack7(rd[idx - ldz], pr);  // N1: (x, y-1, z)
+              S[SIY] = max7_literal<SIY, true>(pr, kp, 0, sh, g);
+              w |= g << (3 * SIY);
+              unpack7(rd[idx - 1], pr);  // W1: (x, y, z-1)
+              S[SIZ] = max7_literal<SIZ, true>(pr, kp, 0, sh, g);
+              w |= g << (3 * SIZ);
+              wr[idx] = pack7(S);
+              cube[tb_index(x, y0 + y, z0 + z, la, lc)] = w;
+              if (x == la && y0 + y == lb && z0 + z == lc) {  // FINAL_MAX, src/TriAlign_1cyc.v:141-142
+                int32_t m = S[0];
+#pragma unroll
+                for (int s = 1; s < NSTATE; ++s) m = max(m, S[s]);
+                scores[t] = m;
+#pragma unroll
+                for (int s = 0; s < NSTATE; ++s) final7[t * NSTATE + s] = S[s];
+              }
+              hM3[k] = hM2[k];
+              gh[k] = (gh[k] & ~(7u << 9)) | (((gh[k] >> 12) & 7u) << 9);
+            }
+            // what cells x+1 and x+2 take from this step's reads, evaluated now
+            uint32_t gn = gh[k] & (7u << 9);
+            literal_adds(kp, symA(x), b, cc, sh, sab, sbc, sac, s3);  // a_{x+1}
+            unpack7(rd[idx - ldz], pr);  // N1 = (x, y-1, z): Ixy of x+1
+            hXY[k] = max7_literal<SIXY, true>(pr, kp, sab, sh, g);
+            gn |= g;
+            unpack7(rd[idx - 1], pr);  // W1 = (x, y, z-1): Ixz of x+1
+            hXZ[k] = max7_literal<SIXZ, true>(pr, kp, sac, sh, g);
+            gn |= g << 6;
+            unpack7(rd[idx - ldz - 1], pr);  // NW1 = (x+1, y-1, z-1): Iyz of x+1, M of x+2
+            hYZ[k] = max7_literal<SIYZ, true>(pr, kp, sbc, sh, g);
+            gn |= g << 3;
+            literal_adds(kp, symA(x + 1), b, cc, sh, sab, sbc, sac, s3);  // a_{x+2}
+            hM2[k] = max7_literal<SM, true>(pr, kp, s3, sh, g);
+            gh[k] = gn | (g << 12);
+          }
+        }
+        // face work, off the cell's registers: f = 0 the corner, 1 .. tzl row 0
+        // and the last local row, tzl+1 .. tzl+tyl column 0 and the last local
+        // column. A face position publishes its cell of this step; a position of
+        // the last row / column hands on what it published last step (x = q-1-y-z,
+        // stable in rd), which is why a tile with a face to write runs one step more.
+        for (int32_t f = tid; f <= tzl + tyl; f += nt) {
+          const bool row = f <= tzl;
+          const int32_t y = row ? 0 : f - tzl, z = row ? f : 0;
+          const int32_t x = q - y - z;
+          const uint4 *src = row ? ((f || zrd) ? yrd : nullptr) : zrd;  // the corner of a first column is zero
+          if (src && x >= 1 && x <= la)
+            wr[y * ldz + z] = src[row ? (int64_t)(x - 1) * (lc + 1) + z0 + z : (int64_t)(x - 1) * TY + (y - 1)];
+          const int32_t sy = row ? tyl : y, sz = row ? z : tzl;
+          const int32_t sx = q - 1 - sy - sz;
+          uint4 *dst = row ? ywr : zwr;
+          if (f && dst && sx >= 1 && sx <= la)
+            dst[row ? (int64_t)(sx - 1) * (lc + 1) + z0 + sz : (int64_t)(sx - 1) * TY + (sy - 1)] = rd[sy * ldz + sz];
+        }
+        __syncthreads();
+      }
+    }
+}
+
+// One launch for n triples, triple = workgroup, each swept in tiles of at most
+// tymax x tzmax (which must pass align_tile_fits). max_pos = the largest
+// TY*TZ of the batch's tile geometries and lds = the largest
+// align_resident_lds(la, TY, TZ). d_face_off[t] is the cell offset of triple
+// t's align_tiled_face_cells in d_faces.
+int align_launch_tiled(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, int32_t tymax, int32_t tzmax,
+                       int64_t max_pos, size_t lds, const KParams &kp, int32_t *d_scores, int32_t *d_final7,
+                       uint32_t *d_tb, const int64_t *d_tb_off, void *d_faces, const int64_t *d_face_off,
+                       hipStream_t stream) {
+  if (n <= 0) return TSA_OK;
+  if (!align_tile_fits(tymax, tzmax) || max_pos < 1 || max_pos > (int64_t)tymax * tzmax || lds > LDS_MAX || !d_tb ||
+      !d_tb_off || !d_faces || !d_face_off)
+    return TSA_EINVAL;
+  const int k = (int)((max_pos + TILED_NT - 1) / TILED_NT);
+  const int nt = (int)(((max_pos + k - 1) / k + 63) / 64 * 64);
+  auto launch = [&](auto kfn) {
+    return launch_with_lds((const void *)kfn, lds, [&] {
+             hipLaunchKernelGGL(kfn, dim3(n), dim3(nt), lds, stream, d_seqs, d_offsets, kp, (uint32_t)lds, tymax,
+                                tzmax, d_scores, d_final7, d_tb, d_tb_off, (uint4 *)d_faces, d_face_off);
+           }) == hipSuccess
+               ? TSA_OK
+               : TSA_EDEVICE;
+  };
+  if (k == 1) return launch(align_tiled_kernel<1>);
+  if (k == 2) return launch(align_tiled_kernel<2>);
+  return launch(align_tiled_kernel<3>);
+}
+
+}  // namespace tsa

@@ -248,7 +248,15 @@ int tsa_align_gpu(const uint8_t *a, int32_t la, const uint8_t *b, int32_t lb,
  * 32*(lb+1)*(lc+1) + lb + lc bytes within the 160 KiB of LDS; 64 x 64 fits,
  * LA is unbounded) is swept by the resident kernel, one launch for all such
  * triples of a chunk; the others run the plane sweep, one launch per plane for
- * all of them (override align_mode). The pointer cubes cost 4*lb*(la+lc-1)*lc
+ * all of them (override align_mode). When a chunk holds at least 256 triples
+ * that do not fit, or under align_mode = tiled for any number of them, they
+ * are swept by the tiled resident kernel instead: one workgroup per triple
+ * sweeps the (y,z) plane in balanced tiles of at most 64 x 48 (or the override
+ * align_tile), one after another, and hands the last row and the last column
+ * of a tile to its neighbours through a face workspace in device memory
+ * (32*la*(lc+1) + 32*la*TY bytes per triple, TY the tile's rows); one more
+ * launch per chunk, results identical (tsa_describe_align_plan names the
+ * path). The pointer cubes cost 4*lb*(la+lc-1)*lc
  * bytes per triple: the batch is processed in chunks of consecutive triples
  * whose cubes fit a budget -- half of the device memory free at the call, or
  * the override align_tb_bytes -- and a triple whose own cube exceeds the
@@ -257,6 +265,17 @@ int tsa_align_gpu(const uint8_t *a, int32_t la, const uint8_t *b, int32_t lb,
 int tsa_align_batch(const uint8_t *seqs, const int64_t *offsets, int32_t n,
                     const tsa_params *p, int32_t *scores, uint8_t *moves,
                     int32_t *n_moves, int32_t *starts, int32_t device);
+
+/* Which path tsa_align_batch takes for a group (one chunk) of n triples of
+ * these lengths under the current overrides, as a short text that begins with
+ * "resident", "tiled" or "plane"; for tiled it carries the tile and the tile
+ * grid, such as "tiled tile=64x43 tiles=4x6 lds=91632 faces=5259264" (lds:
+ * dynamic LDS of the workgroup, faces: bytes of the triple's face workspace).
+ * It is built from the functions the dispatch uses. Host-only, no device
+ * needed. TSA_EINVAL for a null or empty buffer, n or a length below 1, bad
+ * parameters, or an align_mode / align_tile value that is not valid. */
+int tsa_describe_align_plan(int32_t n, int32_t la, int32_t lb, int32_t lc,
+                            const tsa_params *p, char *buf, size_t len);
 
 /* Which kernel, arithmetic and schedule a batch of these sizes would run, as a
  * short text such as "pencil lap f16 rtl M=1 NW=16 laps=16 tiles=1 waves=1"
@@ -279,7 +298,8 @@ int64_t tsa_fallback_count(void);
 int64_t tsa_check_fallback_count(void);
 
 /* Kernel launches with dynamic LDS (helix, lap, literal helix; the resident
- * traceback kernel of tsa_align_batch, one per chunk) the library has queued
+ * and the tiled resident traceback kernel of tsa_align_batch, each one per
+ * chunk that has triples for it) the library has queued
  * since it was loaded: a call that reuses an error left over from an earlier
  * HIP call must still launch its kernel exactly once (tests). The plane sweep
  * and the traceback walks are not counted. */
@@ -313,9 +333,17 @@ const char *tsa_version(void);
  *   lap_spin_limit  polls before a lap hand-off times out (0: at once)
  *   lap_trace       path of a per-workgroup timestamp CSV (tools/lap_trace.py)
  *   split_serial    0 | 1           (tsa_score_gpu_multi parts one by one)
- *   align_mode      resident | plane (tsa_align_batch: resident still sends a
- *                   triple that does not fit a workgroup to the plane sweep)
+ *   align_mode      resident | plane | tiled (tsa_align_batch: resident still
+ *                   sends a triple that does not fit a workgroup to the plane
+ *                   sweep; tiled sends it to the tiled resident kernel, and no
+ *                   triple to the plane sweep)
  *   align_tb_bytes  pointer-cube budget of a tsa_align_batch chunk, in bytes
+ *   align_tile      TYxTZ, e.g. 5x7: caps the tile edges of the tiled kernel;
+ *                   under align_mode = tiled every triple larger than the tile
+ *                   is tiled, even one that would fit a workgroup. A malformed
+ *                   value, an edge below 1 or a tile over the tiled kernel's
+ *                   capacity (the resident capacity, and TY*TZ <= 3072) makes tsa_align_batch and tsa_describe_align_plan return
+ *                   TSA_EINVAL
  * value NULL clears `name`; name NULL clears every override. TSA_EINVAL for an
  * unknown name or a value longer than 255 bytes. The reference has no
  * counterpart: its datapath parameters are fixed at build (src/PE_1cyc.v:55-61). */

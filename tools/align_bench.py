@@ -6,6 +6,8 @@ turn), after warm-up passes that are not timed. All three calls are
 synchronous, so host wall time is the time a caller waits.
   python tools/align_bench.py --n 512 --la 64 --lb 64 --lc 64
   python tools/align_bench.py --n 64 --la 64 --related
+  python tools/align_bench.py --n 256 --la 256 --forms tiled,plane
+(a form other than loop is passed to align_mode as it stands).
 A library without tsa_align_batch (an older build named by TSA_PKG_DIR) runs
 the loop alone: that is how the baseline of a comparison is taken.
 Prints one JSON line: per form the median, min and max of the passes in ms."""
