@@ -1,0 +1,369 @@
+// align_api.hip -- the traceback entry points of include/trialign.h:
+// tsa_align_batch, tsa_align_gpu (one triple, always the plane sweep) and
+// tsa_describe_align_plan. Host code only: which path a triple takes, the
+// chunks of pointer cubes, the device buffers and the launches of the resident
+// kernel (align_kernel.hip), the tiled resident kernel
+// (align_tiled_kernel.hip), the batched plane sweep and the batched walk
+// (plane_kernel.hip).
+//
+// Traceback is an extension: the reference's alignment-output ports are
+// commented out (src/TriAlign_tb.sv:239-260).
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "align_kernel.h"
+
+using namespace tsa;
+
+namespace {
+// Device buffers and the stream of one call, released on every exit path.
+struct AlignBufs {
+  std::vector<void *> ptrs;
+  hipStream_t s = nullptr;
+  template <class T>
+  bool alloc(T **p, size_t bytes) {
+    void *v = nullptr;
+    if (hipMalloc(&v, std::max<size_t>(bytes, 16)) != hipSuccess) return false;
+    ptrs.push_back(v);
+    *p = (T *)v;
+    return true;
+  }
+  ~AlignBufs() {
+    for (void *v : ptrs) (void)hipFree(v);
+    if (s) (void)hipStreamDestroy(s);
+  }
+};
+
+// Which path a triple takes. One that fits a workgroup is swept by the resident
+// kernel (one launch per chunk): on the MI355X it was the faster path on every
+// recorded shape it holds (profiles/align_batch.jsonl). One that does not fit
+// is swept tile by tile by the tiled resident kernel (one more launch per
+// chunk) or by the batched plane sweep. The tiled kernel runs one workgroup
+// per triple, so it needs a group large enough to fill the device: without an
+// override, the over-capacity triples of a chunk are tiled when there are at
+// least kAlignTiledMinGroup of them (profiles/align_tiled.jsonl)
+// and take the plane sweep otherwise.
+enum AlignPath { ALIGN_RESIDENT, ALIGN_TILED, ALIGN_PLANE };
+enum AlignMode { ALIGN_MODE_AUTO, ALIGN_MODE_RESIDENT, ALIGN_MODE_PLANE, ALIGN_MODE_TILED };
+struct AlignPlan {
+  AlignMode mode = ALIGN_MODE_AUTO;
+  bool capped = false;  // align_tile is set
+  int32_t tymax = ALIGN_TILE_Y, tzmax = ALIGN_TILE_Z;
+};
+// 256 = the smallest measured group from which the tiled kernel's median beat the
+// plane sweep's beyond the spread of the passes on every shape (128^3 and 256^3;
+// at 64 triples the plane sweep still wins both): one workgroup per CU.
+constexpr int32_t kAlignTiledMinGroup = 256;
+
+// The overrides align_mode and align_tile; TSA_EINVAL for a value outside
+// include/trialign.h's.
+int align_plan_read(AlignPlan *pl) {
+  char v[64];
+  *pl = AlignPlan();
+  if (override_str("align_mode", v, sizeof v)) {
+    if (!strcmp(v, "resident")) pl->mode = ALIGN_MODE_RESIDENT;
+    else if (!strcmp(v, "plane")) pl->mode = ALIGN_MODE_PLANE;
+    else if (!strcmp(v, "tiled")) pl->mode = ALIGN_MODE_TILED;
+    else return TSA_EINVAL;
+  }
+  if (override_str("align_tile", v, sizeof v)) {  // "TYxTZ", decimal digits only
+    long e[2] = {0, 0};
+    const char *s = v;
+    for (int k = 0; k < 2; ++k) {
+      if (*s < '0' || *s > '9') return TSA_EINVAL;
+      for (; *s >= '0' && *s <= '9'; ++s)
+        if ((e[k] = e[k] * 10 + (*s - '0')) > 65536) return TSA_EINVAL;
+      if (*s != (k ? '\0' : 'x')) return TSA_EINVAL;
+      ++s;
+    }
+    if (!align_tile_fits((int32_t)e[0], (int32_t)e[1])) return TSA_EINVAL;
+    pl->capped = true;
+    pl->tymax = (int32_t)e[0], pl->tzmax = (int32_t)e[1];
+  }
+  return TSA_OK;
+}
+
+// Over capacity: the triple does not go to the resident kernel as a whole.
+// With align_tile set under align_mode = tiled that is any triple larger than
+// the tile (tests put tiny cubes through many tiles that way).
+bool align_over(const AlignPlan &pl, int32_t la, int32_t lb, int32_t lc) {
+  if (pl.mode == ALIGN_MODE_TILED && pl.capped) return lb > pl.tymax || lc > pl.tzmax;
+  return !align_resident_fits(la, lb, lc);
+}
+
+// The path of the over-capacity triples of a group that holds n_over of them.
+AlignPath align_over_path(const AlignPlan &pl, int32_t n_over) {
+  if (pl.mode == ALIGN_MODE_TILED) return ALIGN_TILED;
+  if (pl.mode == ALIGN_MODE_AUTO && n_over >= kAlignTiledMinGroup) return ALIGN_TILED;
+  return ALIGN_PLANE;
+}
+
+AlignPath align_path(const AlignPlan &pl, int32_t la, int32_t lb, int32_t lc, int32_t n_over) {
+  if (pl.mode == ALIGN_MODE_PLANE) return ALIGN_PLANE;
+  if (!align_over(pl, la, lb, lc)) return ALIGN_RESIDENT;
+  return align_over_path(pl, n_over);
+}
+
+// What the call plans for one triple, computed once: the sizing of the
+// buffers, the chunks and the launches all read these numbers.
+struct AlignTriple {
+  int32_t la, lb, lc;
+  bool over;     // not the resident kernel's: tiled or plane, as its chunk decides
+  size_t cube;   // bytes of its pointer cube
+  size_t face;   // 16-byte cells of its face workspace if the chunk is tiled
+  int64_t pos;   // positions of its workgroup: lb*lc, or TY*TZ of an over-capacity triple's tiles
+  size_t lds;    // align_resident_lds of that plane or tile
+};
+// Consecutive triples [i0, i1) whose cubes fit the budget together, as a batch
+// of its own: what its launches and the buffers need.
+struct AlignChunk {
+  int32_t i0, i1, n_over = 0;
+  bool tiled = false;                     // the path of the n_over over-capacity triples
+  size_t cube = 0, seq = 0;               // bytes of the cubes and of the sequences
+  int64_t max_pos = 1, tile_pos = 1;      // the resident and the tiled launch
+  size_t lds = 0, tile_lds = 0, face = 0; // face: bytes
+  int32_t mla = 1, mlb = 1, mlc = 1;      // the plane sweep
+  size_t ws = 0;
+};
+
+// The traceback of n validated triples on the current device: plan pl, chunks
+// of at most `budget` bytes of pointer cubes. Outputs as tsa_align_batch's.
+int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KParams &kp, const AlignPlan &pl,
+              size_t budget, int32_t *scores, uint8_t *moves, int32_t *n_moves, int32_t *starts) {
+  std::vector<AlignTriple> T((size_t)n);
+  for (int32_t i = 0; i < n; ++i) {
+    const int64_t *o = offsets + 3 * (int64_t)i;
+    AlignTriple &t = T[i];
+    t.la = (int32_t)(o[1] - o[0]), t.lb = (int32_t)(o[2] - o[1]), t.lc = (int32_t)(o[3] - o[2]);
+    t.over = align_path(pl, t.la, t.lb, t.lc, 0) != ALIGN_RESIDENT;
+    t.cube = tb_cube_bytes(t.la, t.lb, t.lc);
+    const AlignTileGeom g = t.over ? align_tile_geom(t.lb, t.lc, pl.tymax, pl.tzmax) : AlignTileGeom{t.lb, t.lc, 1, 1};
+    t.face = t.over ? align_tiled_face_cells(t.la, t.lb, t.lc, pl.tymax, pl.tzmax) : 0;
+    t.pos = (int64_t)g.TY * g.TZ;
+    t.lds = align_resident_lds(t.la, g.TY, g.TZ);
+  }
+  std::vector<AlignChunk> chunks;
+  size_t max_cube = 0, max_seq = 0, max_ws = 0, max_face = 0;
+  int32_t max_n = 0;
+  for (int32_t i = 0; i < n;) {
+    AlignChunk c;  // the over-capacity triples' needs for both of their paths, until their number decides
+    int32_t j = i;
+    for (; j < n && j - i < 65535; ++j) {
+      const AlignTriple &t = T[j];
+      if (t.cube > budget) return TSA_ENOMEM;  // one cube over the budget, as a failed allocation
+      if (t.cube > budget - c.cube) break;
+      c.cube += t.cube;
+      c.seq += (size_t)t.la + t.lb + t.lc;
+      if (!t.over) {
+        c.max_pos = std::max(c.max_pos, t.pos), c.lds = std::max(c.lds, t.lds);
+        continue;
+      }
+      ++c.n_over;
+      c.tile_pos = std::max(c.tile_pos, t.pos), c.tile_lds = std::max(c.tile_lds, t.lds);
+      c.face += sizeof(uint4) * t.face;
+      c.mla = std::max(c.mla, t.la), c.mlb = std::max(c.mlb, t.lb), c.mlc = std::max(c.mlc, t.lc);
+    }
+    c.i0 = i, c.i1 = j;
+    c.tiled = c.n_over && align_over_path(pl, c.n_over) == ALIGN_TILED;
+    if (!c.tiled) c.face = 0, c.ws = c.n_over ? plane_workspace_bytes(c.n_over, c.mla, c.mlb, c.mlc) : 0;
+    chunks.push_back(c);
+    max_cube = std::max(max_cube, c.cube), max_seq = std::max(max_seq, c.seq);
+    max_ws = std::max(max_ws, c.ws), max_face = std::max(max_face, c.face);
+    max_n = std::max(max_n, j - i);
+    i = j;
+  }
+  // device buffers, once per call, sized for the largest chunk
+  AlignBufs B;
+  uint8_t *d_seqs = nullptr, *d_moves = nullptr;
+  int64_t *d_meta = nullptr;  // [0, 3m] offsets, then m cube word offsets, then m face cell offsets
+  int32_t *d_res = nullptr;   // m scores, 7m final states, 4m walk infos
+  uint32_t *d_tb = nullptr;
+  void *d_ws = nullptr, *d_faces = nullptr;
+  if (hipStreamCreateWithFlags(&B.s, hipStreamNonBlocking) != hipSuccess) return TSA_EDEVICE;
+  if (!B.alloc(&d_seqs, max_seq) || !B.alloc(&d_moves, max_seq) ||
+      !B.alloc(&d_meta, sizeof(int64_t) * (5 * (size_t)max_n + 1)) ||
+      !B.alloc(&d_res, sizeof(int32_t) * 12 * (size_t)max_n) || !B.alloc(&d_tb, max_cube) ||
+      !B.alloc(&d_ws, max_ws) || !B.alloc(&d_faces, max_face))
+    return TSA_ENOMEM;
+  std::vector<uint8_t> h_seqs(max_seq), h_moves(max_seq);
+  std::vector<int64_t> h_meta(5 * (size_t)max_n + 1);
+  std::vector<int32_t> h_res(12 * (size_t)max_n), order((size_t)max_n);
+  for (const AlignChunk &c : chunks) {
+    // resident triples first, then the over-capacity ones (tiled or plane, one
+    // path for all of a chunk), packed back to back, so each path sees a
+    // contiguous sub-batch
+    const int32_t m = c.i1 - c.i0, mr = m - c.n_over;
+    int32_t r = 0, v = mr;
+    for (int32_t i = c.i0; i < c.i1; ++i) order[T[i].over ? v++ : r++] = i;
+    int64_t pos = 0, word = 0, cells = 0;
+    int64_t *h_off = h_meta.data(), *h_tboff = h_meta.data() + 3 * (size_t)m + 1, *h_faceoff = h_tboff + m;
+    for (int32_t j = 0; j < m; ++j) {
+      const AlignTriple &t = T[order[j]];
+      std::memcpy(h_seqs.data() + pos, seqs + offsets[3 * (int64_t)order[j]], (size_t)t.la + t.lb + t.lc);
+      h_off[3 * j] = pos, h_off[3 * j + 1] = pos + t.la, h_off[3 * j + 2] = pos + t.la + t.lb;
+      pos += (int64_t)t.la + t.lb + t.lc;
+      h_tboff[j] = word;
+      word += (int64_t)(t.cube / sizeof(uint32_t));
+      h_faceoff[j] = cells;
+      if (c.tiled) cells += (int64_t)t.face;
+    }
+    h_off[3 * m] = pos;
+    int32_t *d_scores = d_res, *d_final7 = d_res + m, *d_info = d_res + 8 * (size_t)m;
+    const int64_t *d_off = d_meta, *d_tboff = d_meta + 3 * (size_t)m + 1, *d_faceoff = d_tboff + m;
+    if (hipMemcpyAsync(d_seqs, h_seqs.data(), (size_t)pos, hipMemcpyHostToDevice, B.s) != hipSuccess ||
+        hipMemcpyAsync(d_meta, h_meta.data(), sizeof(int64_t) * (5 * (size_t)m + 1), hipMemcpyHostToDevice, B.s) !=
+            hipSuccess)
+      return TSA_EDEVICE;
+    int rc = TSA_OK;
+    if (mr && (rc = align_launch_resident(d_seqs, d_off, mr, c.max_pos, c.lds, kp, d_scores, d_final7, d_tb, d_tboff,
+                                          B.s)))
+      return rc;
+    if (c.tiled)
+      rc = align_launch_tiled(d_seqs, d_off + 3 * (size_t)mr, c.n_over, pl.tymax, pl.tzmax, c.tile_pos, c.tile_lds, kp,
+                              d_scores + mr, d_final7 + (size_t)NSTATE * mr, d_tb, d_tboff + mr, d_faces,
+                              d_faceoff + mr, B.s);
+    else if (c.n_over)
+      rc = plane_launch_batch(d_seqs, d_off + 3 * (size_t)mr, c.n_over, c.mla, c.mlb, c.mlc, kp, d_scores + mr,
+                              d_final7 + (size_t)NSTATE * mr, d_ws, c.ws, B.s, d_tb, d_tboff + mr);
+    if (rc) return rc;
+    hipLaunchKernelGGL(tb_walk_batch, dim3((m + 63) / 64), dim3(64), 0, B.s, d_tb, d_tboff, d_off, m, d_final7, d_moves,
+                       d_info);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(h_res.data(), d_res, sizeof(int32_t) * 12 * (size_t)m, hipMemcpyDeviceToHost, B.s) !=
+            hipSuccess ||
+        hipMemcpyAsync(h_moves.data(), d_moves, (size_t)pos, hipMemcpyDeviceToHost, B.s) != hipSuccess ||
+        hipStreamSynchronize(B.s) != hipSuccess)
+      return TSA_EDEVICE;
+    for (int32_t j = 0; j < m; ++j) {
+      const int32_t i = order[j];
+      const int32_t *info = h_res.data() + 8 * (size_t)m + 4 * (size_t)j;
+      const int64_t len = offsets[3 * (int64_t)i + 3] - offsets[3 * (int64_t)i];
+      if (info[0] < 1 || info[0] > len) return TSA_EINTERNAL;
+      std::memcpy(moves + (offsets[3 * (int64_t)i] - offsets[0]), h_moves.data() + h_off[3 * j], (size_t)info[0]);
+      scores[i] = h_res[j];
+      n_moves[i] = info[0];
+      starts[3 * (int64_t)i] = info[1], starts[3 * (int64_t)i + 1] = info[2], starts[3 * (int64_t)i + 2] = info[3];
+    }
+  }
+  return TSA_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int tsa_describe_align_plan(int32_t n, int32_t la, int32_t lb, int32_t lc, const tsa_params *p, char *buf,
+                            size_t len) {
+  if (!buf || len == 0 || n < 1 || la < 1 || lb < 1 || lc < 1 || !params_ok(p)) return TSA_EINVAL;
+  AlignPlan pl;
+  int rc = align_plan_read(&pl);
+  if (rc) return rc;
+  switch (align_path(pl, la, lb, lc, n)) {
+    case ALIGN_RESIDENT:
+      snprintf(buf, len, "resident lds=%zu", align_resident_lds(la, lb, lc));
+      break;
+    case ALIGN_TILED: {
+      const AlignTileGeom g = align_tile_geom(lb, lc, pl.tymax, pl.tzmax);
+      snprintf(buf, len, "tiled tile=%dx%d tiles=%dx%d lds=%zu faces=%zu", g.TY, g.TZ, g.nty, g.ntz,
+               align_resident_lds(la, g.TY, g.TZ), 16 * align_tiled_face_cells(la, lb, lc, pl.tymax, pl.tzmax));
+      break;
+    }
+    default:
+      snprintf(buf, len, "plane");
+  }
+  return TSA_OK;
+}
+
+int tsa_align_batch(const uint8_t *seqs, const int64_t *offsets, int32_t n, const tsa_params *p,
+                    int32_t *scores, uint8_t *moves, int32_t *n_moves, int32_t *starts, int32_t device) {
+  if (!seqs || !offsets || !scores || !moves || !n_moves || !starts || n < 0 || !params_ok(p)) return TSA_EINVAL;
+  for (int32_t i = 0; i < n; ++i) {
+    const int64_t *o = offsets + 3 * (int64_t)i;
+    if (o[1] < o[0] || o[2] < o[1] || o[3] < o[2]) return TSA_EINVAL;
+    int rc = tsa_validate(seqs + o[0], (int32_t)(o[1] - o[0]), seqs + o[1], (int32_t)(o[2] - o[1]),
+                          seqs + o[2], (int32_t)(o[3] - o[2]), p);
+    if (rc) return rc;
+  }
+  if (n == 0) return TSA_OK;
+  const int nd = tsa_device_count();
+  if (nd <= 0) return TSA_ENODEV;
+  if (device < 0 || device >= nd) return TSA_ENODEV;
+  KParams kp;
+  int rc = build_kparams(p, &kp);
+  if (rc) return rc;
+  AlignPlan pl;
+  if ((rc = align_plan_read(&pl))) return rc;
+  if (hipSetDevice(device) != hipSuccess) return TSA_EDEVICE;
+  // The pointer-cube budget of a chunk: align_tb_bytes, or half of the device
+  // memory free at the call (the other half is left to the caller's own
+  // buffers and to the sequences, moves, plane rings and tile faces of the
+  // chunk, all of which are O(N^2) against the cubes' O(N^3)).
+  size_t budget = 0;
+  long ov = 0;
+  if (override_int("align_tb_bytes", &ov)) {
+    if (ov < 0) return TSA_EINVAL;
+    budget = (size_t)ov;
+  } else {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return TSA_EDEVICE;
+    budget = free_b / 2;
+  }
+  return align_run(seqs, offsets, n, kp, pl, budget, scores, moves, n_moves, starts);
+}
+
+// One triple, always by the plane sweep, with buffers and a one-thread walk of
+// its own: it reads no override and has no cube budget. As a batch of one
+// through align_run it measured 0.1-0.3 ms slower per call.
+int tsa_align_gpu(const uint8_t *a, int32_t la, const uint8_t *b, int32_t lb, const uint8_t *c,
+                  int32_t lc, const tsa_params *p, int32_t *score, uint8_t *moves, int32_t max_moves,
+                  int32_t *n_moves, int32_t *start, int32_t device) {
+  if (!score || !moves || !n_moves || !start) return TSA_EINVAL;
+  int rc = tsa_validate(a, la, b, lb, c, lc, p);
+  if (rc) return rc;
+  if ((int64_t)max_moves < (int64_t)la + lb + lc) return TSA_EINVAL;
+  const int nd = tsa_device_count();
+  if (nd <= 0) return TSA_ENODEV;
+  if (device < 0 || device >= nd) return TSA_ENODEV;
+  KParams kp;
+  if ((rc = build_kparams(p, &kp))) return rc;
+  const int64_t len = (int64_t)la + lb + lc;
+  const int64_t off[4] = {0, la, (int64_t)la + lb, len};
+  const size_t ws_bytes = plane_workspace_bytes(1, la, lb, lc);
+  AlignBufs B;
+  uint8_t *d_seqs = nullptr, *d_moves = nullptr;
+  int64_t *d_off = nullptr;
+  int32_t *d_small = nullptr, h_small[12];  // [0] score, [1..7] final states, [8..11] walk info
+  uint32_t *d_tb = nullptr;
+  void *d_ws = nullptr;
+  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&B.s, hipStreamNonBlocking) != hipSuccess)
+    return TSA_EDEVICE;
+  if (!B.alloc(&d_seqs, (size_t)len) || !B.alloc(&d_off, sizeof(off)) || !B.alloc(&d_small, sizeof(h_small)) ||
+      !B.alloc(&d_moves, (size_t)len) || !B.alloc(&d_ws, ws_bytes) || !B.alloc(&d_tb, tb_cube_bytes(la, lb, lc)))
+    return TSA_ENOMEM;
+  if (hipMemcpyAsync(d_seqs, a, la, hipMemcpyHostToDevice, B.s) != hipSuccess ||
+      hipMemcpyAsync(d_seqs + la, b, lb, hipMemcpyHostToDevice, B.s) != hipSuccess ||
+      hipMemcpyAsync(d_seqs + la + lb, c, lc, hipMemcpyHostToDevice, B.s) != hipSuccess ||
+      hipMemcpyAsync(d_off, off, sizeof(off), hipMemcpyHostToDevice, B.s) != hipSuccess)
+    return TSA_EDEVICE;
+  if ((rc = plane_launch_batch(d_seqs, d_off, 1, la, lb, lc, kp, d_small, d_small + 1, d_ws, ws_bytes, B.s, d_tb)))
+    return rc;
+  hipLaunchKernelGGL(tb_walk, dim3(1), dim3(64), 0, B.s, d_tb, d_small + 1, la, lb, lc, d_moves, d_small + 8);
+  if (hipGetLastError() != hipSuccess ||
+      hipMemcpyAsync(h_small, d_small, sizeof(h_small), hipMemcpyDeviceToHost, B.s) != hipSuccess ||
+      hipStreamSynchronize(B.s) != hipSuccess)
+    return TSA_EDEVICE;
+  if (h_small[8] < 1 || h_small[8] > len) return TSA_EINTERNAL;
+  std::vector<uint8_t> rev((size_t)h_small[8]);  // tb_walk gives the moves from the end backwards
+  if (hipMemcpy(rev.data(), d_moves, rev.size(), hipMemcpyDeviceToHost) != hipSuccess) return TSA_EDEVICE;
+  for (size_t k = 0; k < rev.size(); ++k) moves[k] = rev[rev.size() - 1 - k];
+  *score = h_small[0];
+  *n_moves = h_small[8];
+  start[0] = h_small[9], start[1] = h_small[10], start[2] = h_small[11];
+  return TSA_OK;
+}
+
+}  // extern "C"

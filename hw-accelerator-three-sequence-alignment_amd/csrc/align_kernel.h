@@ -1,11 +1,15 @@
-// align_kernel.h -- host interface of batched traceback (tsa_align_batch): the
-// resident kernel (align_kernel.hip), the batch form of the TB plane sweep and
-// the batched walk (plane_kernel.hip).
+// align_kernel.h -- what the traceback entry points (align_api.hip) launch: the
+// resident kernel (align_kernel.hip), the tiled resident kernel
+// (align_tiled_kernel.hip), the batch form of the TB plane sweep and the
+// batched walk (plane_kernel.hip).
 #pragma once
 
 #include "tsa_internal.h"
 
 namespace tsa {
+
+// trialign_api.hip's check of a parameter set (1 = usable).
+int params_ok(const tsa_params *p);
 
 // The TB plane sweep for a batch: triple t's pointer cube starts at word
 // d_tb_off[t] of d_tb, one launch per plane serves all n triples (max_l* over

@@ -14,10 +14,8 @@
 // (align_tile_geom); the workgroup of a triple sweeps them ty outer, tz inner,
 // so tiles (ty-1,tz), (ty,tz-1) and (ty-1,tz-1) are finished when (ty,tz)
 // starts. A tile is swept over all x by the resident schedule of
-// align_kernel.hip in local coordinates: step q, local position (y,z) at
-// x = q-y-z, two zeroed LDS buffers of 16-byte cells with a row 0 and a column
-// 0, publication only while 1 <= x <= la, the 5-state register history, one
-// barrier per step. What differs is what row 0 and column 0 hold. In the first
+// align_kernel.hip in local coordinates, through the same step (align_step.h).
+// What differs is what row 0 and column 0 of the buffers hold. In the first
 // tile row / column they are the zero faces and nothing is published. In every
 // other tile the face position (0,z) is at x = q-z, (y,0) at x = q-y and the
 // corner (0,0) at x = q, and while 1 <= x <= la it publishes into buf[q&1] the
@@ -40,7 +38,7 @@
 // another: there is no flag, fence or poll.
 
 #include "align_kernel.h"
-#include "literal_cell.h"
+#include "align_step.h"
 #include "pencil_common.h"
 
 namespace tsa {
@@ -73,21 +71,14 @@ __global__ __launch_bounds__(TILED_NT) void align_tiled_kernel(
   const int tid = threadIdx.x, nt = blockDim.x;
   uint4 *buf0 = (uint4 *)smem, *buf1 = buf0 + ncell;
   uint8_t *sym = (uint8_t *)(buf1 + ncell);
-  // A staged only when the launch's LDS has room for it
-  const bool a_lds = 2 * sizeof(uint4) * (size_t)ncell + (size_t)TY + TZ + la <= lds_bytes;
-  uint8_t *sB = sym, *sC = sym + TY;
-  const uint8_t *sA = sym + TY + TZ;
-  if (a_lds)
-    for (int32_t i = tid; i < la; i += nt) sym[TY + TZ + i] = (uint8_t)tsa_sym(seqs, o0 + i, kp.packed);
+  uint8_t *sB = sym, *sC = sym + TY, *sA = sym + TY + TZ;
+  const bool a_lds = align_stage_a(sA, 2 * sizeof(uint4) * (size_t)ncell + TY + TZ, lds_bytes, seqs, o0, la, kp.packed,
+                                   tid, nt);
+  const auto symA = align_sym_a(a_lds, sA, seqs, o0, la, kp);
   // the face workspace of this triple: y faces [2][la][lc+1], z faces [2][la][TY]
   const int64_t ysz = (int64_t)la * (lc + 1), zsz = (int64_t)la * TY;
   uint4 *yf = faces + face_off[t], *zf = yf + 2 * ysz;
   uint32_t *cube = tb + tb_off[t];
-  const int32_t sh = kp.wrap_shift;
-  auto symA = [&](int32_t i) {  // a_{i+1}, the index clamped into the sequence
-    i = min(max(i, 0), la - 1);
-    return a_lds ? (int)sA[i] : (int)tsa_sym(seqs, o0 + i, kp.packed);
-  };
   for (int32_t ty = 0; ty < tg.nty; ++ty)
     for (int32_t tz = 0; tz < tg.ntz; ++tz) {
       const int32_t y0 = ty * TY, z0 = tz * TZ;
@@ -103,86 +94,19 @@ __global__ __launch_bounds__(TILED_NT) void align_tiled_kernel(
       const uint4 *zrd = tz ? zf + ((tz - 1) & 1) * zsz : nullptr;
       uint4 *ywr = ty + 1 < tg.nty ? yf + (ty & 1) * ysz : nullptr;
       uint4 *zwr = tz + 1 < tg.ntz ? zf + (tz & 1) * zsz : nullptr;
-      // position k of this thread: y | z << 13 | b << 26 | c << 28 | valid << 30 (local y, z)
-      uint32_t meta[K], gh[K];                         // gh: the 5 kept argmaxes, 3 bits each
-      int32_t hXY[K], hYZ[K], hXZ[K], hM3[K], hM2[K];  // the kept states
+      // the positions in local y, z; the history starts again
+      uint32_t meta[K], gh[K];
+      int32_t hXY[K], hYZ[K], hXZ[K], hM3[K], hM2[K];
+      auto P = [&](int k) { return AlignPos{meta[k], gh[k], hXY[k], hYZ[k], hXZ[k], hM3[k], hM2[k]}; };
 #pragma unroll
-      for (int k = 0; k < K; ++k) {
-        const int32_t p = k * nt + tid;
-        meta[k] = 0;
-        if (p < tyl * tzl) {
-          const int32_t y = p / tzl + 1, z = p % tzl + 1;
-          meta[k] = (uint32_t)y | ((uint32_t)z << 13) | ((uint32_t)sB[y - 1] << 26) | ((uint32_t)sC[z - 1] << 28) |
-                    (1u << 30);
-        }
-        gh[k] = 0;
-        hXY[k] = hYZ[k] = hXZ[k] = hM3[k] = hM2[k] = 0;
-      }
+      for (int k = 0; k < K; ++k) P(k).init(k * nt + tid, tyl, tzl, sB, sC);
       const int32_t qmax = la + tyl + tzl + ((ywr || zwr) ? 1 : 0);
       for (int32_t q = 1; q <= qmax; ++q) {
         const uint4 *rd = (q & 1) ? buf0 : buf1;  // buf[(q-1)&1]
         uint4 *wr = (q & 1) ? buf1 : buf0;        // buf[q&1]
 #pragma unroll
-        for (int k = 0; k < K; ++k) {
-          const int32_t y = (int32_t)(meta[k] & 0x1FFFu), z = (int32_t)((meta[k] >> 13) & 0x1FFFu);
-          const int32_t x = q - y - z;
-          if ((meta[k] >> 30) && x >= 0 && x <= la) {
-            const int32_t idx = y * ldz + z;
-            const int b = (int)((meta[k] >> 26) & 3u), cc = (int)((meta[k] >> 28) & 3u);
-            int32_t pr[7], sab, sbc, sac, s3;
-            uint32_t g;
-            if (x == 0) {  // M of x = 1 comes from the corner of the zero x = 0 face
-              const int32_t zero7[7] = {0, 0, 0, 0, 0, 0, 0};
-              literal_adds(kp, symA(0), b, cc, sh, sab, sbc, sac, s3);
-              hM3[k] = max7_literal<SM, true>(zero7, kp, s3, sh, g);
-              gh[k] = (gh[k] & ~(7u << 9)) | (g << 9);
-            } else {
-              int32_t S[7];
-              uint32_t w = (gh[k] & 7u) << (3 * SIXY) | ((gh[k] >> 3) & 7u) << (3 * SIYZ) |
-                           ((gh[k] >> 6) & 7u) << (3 * SIXZ) | ((gh[k] >> 9) & 7u) << (3 * SM);
-              S[SM] = hM3[k];
-              S[SIXY] = hXY[k];
-              S[SIYZ] = hYZ[k];
-              S[SIXZ] = hXZ[k];
-              unpack7(rd[idx], pr);  // own: (x-1, y, z)
-              S[SIX] = max7_literal<SIX, true>(pr, kp, 0, sh, g);
-              w |= g << (3 * SIX);
-              unpack7(rd[idx - ldz], pr);  // N1: (x, y-1, z)
-              S[SIY] = max7_literal<SIY, true>(pr, kp, 0, sh, g);
-              w |= g << (3 * SIY);
-              unpack7(rd[idx - 1], pr);  // W1: (x, y, z-1)
-              S[SIZ] = max7_literal<SIZ, true>(pr, kp, 0, sh, g);
-              w |= g << (3 * SIZ);
-              wr[idx] = pack7(S);
-              cube[tb_index(x, y0 + y, z0 + z, la, lc)] = w;
-              if (x == la && y0 + y == lb && z0 + z == lc) {  // FINAL_MAX, src/TriAlign_1cyc.v:141-142
-                int32_t m = S[0];
-#pragma unroll
-                for (int s = 1; s < NSTATE; ++s) m = max(m, S[s]);
-                scores[t] = m;
-#pragma unroll
-                for (int s = 0; s < NSTATE; ++s) final7[t * NSTATE + s] = S[s];
-              }
-              hM3[k] = hM2[k];
-              gh[k] = (gh[k] & ~(7u << 9)) | (((gh[k] >> 12) & 7u) << 9);
-            }
-            // what cells x+1 and x+2 take from this step's reads, evaluated now
-            uint32_t gn = gh[k] & (7u << 9);
-            literal_adds(kp, symA(x), b, cc, sh, sab, sbc, sac, s3);  // a_{x+1}
-            unpack7(rd[idx - ldz], pr);  // N1 = (x, y-1, z): Ixy of x+1
-            hXY[k] = max7_literal<SIXY, true>(pr, kp, sab, sh, g);
-            gn |= g;
-            unpack7(rd[idx - 1], pr);  // W1 = (x, y, z-1): Ixz of x+1
-            hXZ[k] = max7_literal<SIXZ, true>(pr, kp, sac, sh, g);
-            gn |= g << 6;
-            unpack7(rd[idx - ldz - 1], pr);  // NW1 = (x+1, y-1, z-1): Iyz of x+1, M of x+2
-            hYZ[k] = max7_literal<SIYZ, true>(pr, kp, sbc, sh, g);
-            gn |= g << 3;
-            literal_adds(kp, symA(x + 1), b, cc, sh, sab, sbc, sac, s3);  // a_{x+2}
-            hM2[k] = max7_literal<SM, true>(pr, kp, s3, sh, g);
-            gh[k] = gn | (g << 12);
-          }
-        }
+        for (int k = 0; k < K; ++k)
+          P(k).step(rd, wr, ldz, q, la, y0, z0, lb, lc, cube, kp, t, scores, final7, symA);
         // face work, off the cell's registers: f = 0 the corner, 1 .. tzl row 0
         // and the last local row, tzl+1 .. tzl+tyl column 0 and the last local
         // column. A face position publishes its cell of this step; a position of

@@ -1,7 +1,7 @@
 // literal_cell.h -- the literal cell of the traceback kernels: a 16-byte state
 // cell unpacked, the literal MAX7 with its argmax, and the pointer cube index.
 // Shared by the plane sweep (plane_kernel.hip) and the resident traceback
-// kernel (align_kernel.hip), which must pick the same winner at every cell.
+// kernels (align_step.h), which must pick the same winner at every cell.
 #pragma once
 
 #include "tsa_internal.h"

@@ -19,7 +19,7 @@
 #include <vector>
 
 #include "tsa_internal.h"
-#include "align_kernel.h"
+#include "align_kernel.h"  // declares params_ok for align_api.hip
 #include "pencil_kernel.h"
 #include "lap_kernel.h"
 
@@ -35,7 +35,7 @@ static inline int64_t wrap64(int64_t v, int bits) {
   return (int64_t)u >> (64 - bits);
 }
 
-static int params_ok(const tsa_params *p) {
+int params_ok(const tsa_params *p) {
   if (!p) return 0;
   if (p->s3_mode != TSA_S3_RTL && p->s3_mode != TSA_S3_SOP) return 0;
   if (p->score_bits != 0 && (p->score_bits < 4 || p->score_bits > 16)) return 0;
@@ -806,360 +806,6 @@ int tsa_score_gpu_multi(const uint8_t *a, int32_t la, const uint8_t *b, int32_t 
     rc = score_gpu_multi(a, la, b, lb, c, lc, p, devices, n_devices, score, wall_us, false, &concurrent);
   }
   return rc;
-}
-
-int tsa_align_gpu(const uint8_t *a, int32_t la, const uint8_t *b, int32_t lb, const uint8_t *c,
-                  int32_t lc, const tsa_params *p, int32_t *score, uint8_t *moves, int32_t max_moves,
-                  int32_t *n_moves, int32_t *start, int32_t device) {
-  if (!score || !moves || !n_moves || !start) return TSA_EINVAL;
-  int rc = tsa_validate(a, la, b, lb, c, lc, p);
-  if (rc) return rc;
-  if ((int64_t)max_moves < (int64_t)la + lb + lc) return TSA_EINVAL;
-  const int nd = tsa_device_count();
-  if (nd <= 0) return TSA_ENODEV;
-  if (device < 0 || device >= nd) return TSA_ENODEV;
-  KParams kp;
-  if ((rc = build_kparams(p, &kp))) return rc;
-  const int64_t len = (int64_t)la + lb + lc;
-  const int64_t off[4] = {0, la, (int64_t)la + lb, len};
-  const size_t ws_bytes = plane_workspace_bytes(1, la, lb, lc);
-  const size_t tb_bytes = tb_cube_bytes(la, lb, lc);
-  uint8_t *d_seqs = nullptr, *d_moves = nullptr;
-  int64_t *d_off = nullptr;
-  int32_t *d_small = nullptr;  // [0] score, [1..7] final states, [8..11] walk info
-  uint32_t *d_tb = nullptr;
-  void *d_ws = nullptr;
-  hipStream_t s = nullptr;
-  int32_t h_small[12];
-  HIPCHK(hipSetDevice(device));
-  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  if (hipMalloc(&d_seqs, len) != hipSuccess || hipMalloc(&d_off, sizeof(off)) != hipSuccess ||
-      hipMalloc(&d_small, sizeof(h_small)) != hipSuccess ||
-      hipMalloc(&d_moves, (size_t)len) != hipSuccess ||
-      hipMalloc(&d_ws, std::max<size_t>(ws_bytes, 16)) != hipSuccess ||
-      hipMalloc(&d_tb, std::max<size_t>(tb_bytes, 16)) != hipSuccess) {
-    rc = TSA_ENOMEM;
-    goto done;
-  }
-  HIPCHK(hipMemcpyAsync(d_seqs, a, la, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d_seqs + la, b, lb, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d_seqs + la + lb, c, lc, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d_off, off, sizeof(off), hipMemcpyHostToDevice, s));
-  rc = plane_launch_batch(d_seqs, d_off, 1, la, lb, lc, kp, d_small, d_small + 1, d_ws, ws_bytes,
-                          s, d_tb);
-  if (rc) goto done;
-  hipLaunchKernelGGL(tb_walk, dim3(1), dim3(64), 0, s, d_tb, d_small + 1, la, lb, lc, d_moves,
-                     d_small + 8);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(h_small, d_small, sizeof(h_small), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (h_small[8] < 1 || h_small[8] > len) {
-    rc = TSA_EINTERNAL;
-    goto done;
-  }
-  {
-    std::vector<uint8_t> rev((size_t)h_small[8]);
-    HIPCHK(hipMemcpy(rev.data(), d_moves, rev.size(), hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < rev.size(); ++k) moves[k] = rev[rev.size() - 1 - k];
-  }
-  *score = h_small[0];
-  *n_moves = h_small[8];
-  start[0] = h_small[9];
-  start[1] = h_small[10];
-  start[2] = h_small[11];
-done:
-  if (d_seqs) (void)hipFree(d_seqs);
-  if (d_off) (void)hipFree(d_off);
-  if (d_small) (void)hipFree(d_small);
-  if (d_moves) (void)hipFree(d_moves);
-  if (d_ws) (void)hipFree(d_ws);
-  if (d_tb) (void)hipFree(d_tb);
-  if (s) (void)hipStreamDestroy(s);
-  return rc;
-}
-
-}  // extern "C"
-
-namespace {
-// Device buffers and the stream of one tsa_align_batch call, released on every
-// exit path.
-struct AlignBufs {
-  std::vector<void *> ptrs;
-  hipStream_t s = nullptr;
-  template <class T>
-  bool alloc(T **p, size_t bytes) {
-    void *v = nullptr;
-    if (hipMalloc(&v, std::max<size_t>(bytes, 16)) != hipSuccess) return false;
-    ptrs.push_back(v);
-    *p = (T *)v;
-    return true;
-  }
-  ~AlignBufs() {
-    for (void *v : ptrs) (void)hipFree(v);
-    if (s) (void)hipStreamDestroy(s);
-  }
-};
-}  // namespace
-
-extern "C" {
-
-// Which path a triple takes. One that fits a workgroup is swept by the resident
-// kernel (one launch per chunk): on the MI355X it was the faster path on every
-// recorded shape it holds (profiles/align_batch.jsonl). One that does not fit
-// is swept tile by tile by the tiled resident kernel (one more launch per
-// chunk) or by the batched plane sweep. The tiled kernel runs one workgroup
-// per triple, so it needs a group large enough to fill the device: without an
-// override, the over-capacity triples of a chunk are tiled when there are at
-// least kAlignTiledMinGroup of them (profiles/align_tiled.jsonl)
-// and take the plane sweep otherwise.
-namespace {
-enum AlignPath { ALIGN_RESIDENT, ALIGN_TILED, ALIGN_PLANE };
-enum AlignMode { ALIGN_MODE_AUTO, ALIGN_MODE_RESIDENT, ALIGN_MODE_PLANE, ALIGN_MODE_TILED };
-struct AlignPlan {
-  AlignMode mode = ALIGN_MODE_AUTO;
-  bool capped = false;  // align_tile is set
-  int32_t tymax = ALIGN_TILE_Y, tzmax = ALIGN_TILE_Z;
-};
-// 256 = the smallest measured group from which the tiled kernel's median beat the
-// plane sweep's beyond the spread of the passes on every shape (128^3 and 256^3;
-// at 64 triples the plane sweep still wins both): one workgroup per CU.
-constexpr int32_t kAlignTiledMinGroup = 256;
-
-// The overrides align_mode and align_tile; TSA_EINVAL for a value outside
-// include/trialign.h's.
-int align_plan_read(AlignPlan *pl) {
-  char v[64];
-  *pl = AlignPlan();
-  if (override_str("align_mode", v, sizeof v)) {
-    if (!strcmp(v, "resident")) pl->mode = ALIGN_MODE_RESIDENT;
-    else if (!strcmp(v, "plane")) pl->mode = ALIGN_MODE_PLANE;
-    else if (!strcmp(v, "tiled")) pl->mode = ALIGN_MODE_TILED;
-    else return TSA_EINVAL;
-  }
-  if (override_str("align_tile", v, sizeof v)) {  // "TYxTZ", decimal digits only
-    long e[2] = {0, 0};
-    const char *s = v;
-    for (int k = 0; k < 2; ++k) {
-      if (*s < '0' || *s > '9') return TSA_EINVAL;
-      for (; *s >= '0' && *s <= '9'; ++s)
-        if ((e[k] = e[k] * 10 + (*s - '0')) > 65536) return TSA_EINVAL;
-      if (*s != (k ? '\0' : 'x')) return TSA_EINVAL;
-      ++s;
-    }
-    if (!align_tile_fits((int32_t)e[0], (int32_t)e[1])) return TSA_EINVAL;
-    pl->capped = true;
-    pl->tymax = (int32_t)e[0], pl->tzmax = (int32_t)e[1];
-  }
-  return TSA_OK;
-}
-
-// Over capacity: the triple does not go to the resident kernel as a whole.
-// With align_tile set under align_mode = tiled that is any triple larger than
-// the tile (tests put tiny cubes through many tiles that way).
-bool align_over(const AlignPlan &pl, int32_t la, int32_t lb, int32_t lc) {
-  if (pl.mode == ALIGN_MODE_TILED && pl.capped) return lb > pl.tymax || lc > pl.tzmax;
-  return !align_resident_fits(la, lb, lc);
-}
-
-// The path of the over-capacity triples of a group that holds n_over of them.
-AlignPath align_over_path(const AlignPlan &pl, int32_t n_over) {
-  if (pl.mode == ALIGN_MODE_TILED) return ALIGN_TILED;
-  if (pl.mode == ALIGN_MODE_AUTO && n_over >= kAlignTiledMinGroup) return ALIGN_TILED;
-  return ALIGN_PLANE;
-}
-
-AlignPath align_path(const AlignPlan &pl, int32_t la, int32_t lb, int32_t lc, int32_t n_over) {
-  if (pl.mode == ALIGN_MODE_PLANE) return ALIGN_PLANE;
-  if (!align_over(pl, la, lb, lc)) return ALIGN_RESIDENT;
-  return align_over_path(pl, n_over);
-}
-
-bool align_takes_resident(const AlignPlan &pl, int32_t la, int32_t lb, int32_t lc) {
-  return align_path(pl, la, lb, lc, 0) == ALIGN_RESIDENT;
-}
-}  // namespace
-
-int tsa_describe_align_plan(int32_t n, int32_t la, int32_t lb, int32_t lc, const tsa_params *p, char *buf,
-                            size_t len) {
-  if (!buf || len == 0 || n < 1 || la < 1 || lb < 1 || lc < 1 || !params_ok(p)) return TSA_EINVAL;
-  AlignPlan pl;
-  int rc = align_plan_read(&pl);
-  if (rc) return rc;
-  switch (align_path(pl, la, lb, lc, n)) {
-    case ALIGN_RESIDENT:
-      snprintf(buf, len, "resident lds=%zu", align_resident_lds(la, lb, lc));
-      break;
-    case ALIGN_TILED: {
-      const AlignTileGeom g = align_tile_geom(lb, lc, pl.tymax, pl.tzmax);
-      snprintf(buf, len, "tiled tile=%dx%d tiles=%dx%d lds=%zu faces=%zu", g.TY, g.TZ, g.nty, g.ntz,
-               align_resident_lds(la, g.TY, g.TZ), 16 * align_tiled_face_cells(la, lb, lc, pl.tymax, pl.tzmax));
-      break;
-    }
-    default:
-      snprintf(buf, len, "plane");
-  }
-  return TSA_OK;
-}
-
-int tsa_align_batch(const uint8_t *seqs, const int64_t *offsets, int32_t n, const tsa_params *p,
-                    int32_t *scores, uint8_t *moves, int32_t *n_moves, int32_t *starts, int32_t device) {
-  if (!seqs || !offsets || !scores || !moves || !n_moves || !starts || n < 0 || !params_ok(p)) return TSA_EINVAL;
-  for (int32_t i = 0; i < n; ++i) {
-    const int64_t *o = offsets + 3 * (int64_t)i;
-    if (o[1] < o[0] || o[2] < o[1] || o[3] < o[2]) return TSA_EINVAL;
-    int rc = tsa_validate(seqs + o[0], (int32_t)(o[1] - o[0]), seqs + o[1], (int32_t)(o[2] - o[1]),
-                          seqs + o[2], (int32_t)(o[3] - o[2]), p);
-    if (rc) return rc;
-  }
-  if (n == 0) return TSA_OK;
-  const int nd = tsa_device_count();
-  if (nd <= 0) return TSA_ENODEV;
-  if (device < 0 || device >= nd) return TSA_ENODEV;
-  KParams kp;
-  int rc = build_kparams(p, &kp);
-  if (rc) return rc;
-  AlignPlan pl;
-  if ((rc = align_plan_read(&pl))) return rc;
-  AlignBufs B;
-  if (hipSetDevice(device) != hipSuccess) return TSA_EDEVICE;
-  // The pointer-cube budget of a chunk: align_tb_bytes, or half of the device
-  // memory free at the call (the other half is left to the caller's own
-  // buffers and to the sequences, moves, plane rings and tile faces of the
-  // chunk, all of which are O(N^2) against the cubes' O(N^3)).
-  size_t budget = 0;
-  long ov = 0;
-  if (override_int("align_tb_bytes", &ov)) {
-    if (ov < 0) return TSA_EINVAL;
-    budget = (size_t)ov;
-  } else {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return TSA_EDEVICE;
-    budget = free_b / 2;
-  }
-  auto len_of = [&](int32_t i, int k) { return (int32_t)(offsets[3 * (int64_t)i + k + 1] - offsets[3 * (int64_t)i + k]); };
-  // chunks of consecutive triples whose cubes fit the budget together
-  std::vector<int32_t> chunk_end;
-  size_t max_cube = 0, max_seq = 0, max_ws = 0, max_face = 0;
-  int32_t max_n = 0;
-  for (int32_t i = 0; i < n;) {
-    size_t cube = 0, seq = 0, face = 0;
-    int32_t j = i, mla = 1, mlb = 1, mlc = 1, no = 0;
-    for (; j < n && j - i < 65535; ++j) {
-      const int32_t la = len_of(j, 0), lb = len_of(j, 1), lc = len_of(j, 2);
-      const size_t c = tb_cube_bytes(la, lb, lc);
-      if (c > budget) return TSA_ENOMEM;  // one cube over the budget, as tsa_align_gpu's failed allocation
-      if (cube + c > budget) break;
-      cube += c;
-      seq += (size_t)la + lb + lc;
-      if (!align_takes_resident(pl, la, lb, lc)) {
-        mla = std::max(mla, la), mlb = std::max(mlb, lb), mlc = std::max(mlc, lc);
-        face += sizeof(uint4) * align_tiled_face_cells(la, lb, lc, pl.tymax, pl.tzmax);
-        ++no;
-      }
-    }
-    chunk_end.push_back(j);
-    max_cube = std::max(max_cube, cube);
-    max_seq = std::max(max_seq, seq);
-    max_n = std::max(max_n, j - i);
-    if (no && align_over_path(pl, no) == ALIGN_TILED) max_face = std::max(max_face, face);
-    else if (no) max_ws = std::max(max_ws, plane_workspace_bytes(no, mla, mlb, mlc));
-    i = j;
-  }
-  // device buffers, once per call, sized for the largest chunk
-  uint8_t *d_seqs = nullptr, *d_moves = nullptr;
-  int64_t *d_meta = nullptr;  // [0, 3m] offsets, then m cube word offsets, then m face cell offsets
-  int32_t *d_res = nullptr;   // m scores, 7m final states, 4m walk infos
-  uint32_t *d_tb = nullptr;
-  void *d_ws = nullptr, *d_faces = nullptr;
-  if (hipStreamCreateWithFlags(&B.s, hipStreamNonBlocking) != hipSuccess) return TSA_EDEVICE;
-  if (!B.alloc(&d_seqs, max_seq) || !B.alloc(&d_moves, max_seq) ||
-      !B.alloc(&d_meta, sizeof(int64_t) * (5 * (size_t)max_n + 1)) ||
-      !B.alloc(&d_res, sizeof(int32_t) * 12 * (size_t)max_n) || !B.alloc(&d_tb, max_cube) ||
-      !B.alloc(&d_ws, max_ws) || !B.alloc(&d_faces, max_face))
-    return TSA_ENOMEM;
-  std::vector<uint8_t> h_seqs(max_seq), h_moves(max_seq);
-  std::vector<int64_t> h_meta(5 * (size_t)max_n + 1);
-  std::vector<int32_t> h_res(12 * (size_t)max_n), order((size_t)max_n);
-  int32_t i0 = 0;
-  for (const int32_t i1 : chunk_end) {
-    // the chunk as a batch of its own: resident triples first, then the
-    // over-capacity ones (tiled or plane, one path for all of a chunk), packed
-    // back to back, so each path sees a contiguous sub-batch
-    const int32_t m = i1 - i0;
-    int32_t mr = 0;
-    for (int32_t i = i0; i < i1; ++i)
-      if (align_takes_resident(pl, len_of(i, 0), len_of(i, 1), len_of(i, 2))) order[mr++] = i;
-    int32_t k = mr;
-    for (int32_t i = i0; i < i1; ++i)
-      if (!align_takes_resident(pl, len_of(i, 0), len_of(i, 1), len_of(i, 2))) order[k++] = i;
-    const bool tiled = m > mr && align_over_path(pl, m - mr) == ALIGN_TILED;
-    int64_t pos = 0, word = 0, max_pos = 1, tile_pos = 1, cells = 0;
-    size_t lds = 0, tile_lds = 0;
-    int32_t mla = 1, mlb = 1, mlc = 1;
-    int64_t *h_off = h_meta.data(), *h_tboff = h_meta.data() + 3 * (size_t)m + 1, *h_faceoff = h_tboff + m;
-    for (int32_t j = 0; j < m; ++j) {
-      const int32_t i = order[j], la = len_of(i, 0), lb = len_of(i, 1), lc = len_of(i, 2);
-      std::memcpy(h_seqs.data() + pos, seqs + offsets[3 * (int64_t)i], (size_t)la + lb + lc);
-      h_off[3 * j] = pos, h_off[3 * j + 1] = pos + la, h_off[3 * j + 2] = pos + la + lb;
-      pos += (int64_t)la + lb + lc;
-      h_tboff[j] = word;
-      word += (int64_t)(tb_cube_bytes(la, lb, lc) / sizeof(uint32_t));
-      h_faceoff[j] = cells;
-      if (j < mr) {
-        max_pos = std::max<int64_t>(max_pos, (int64_t)lb * lc);
-        lds = std::max(lds, align_resident_lds(la, lb, lc));
-      } else if (tiled) {
-        const AlignTileGeom g = align_tile_geom(lb, lc, pl.tymax, pl.tzmax);
-        tile_pos = std::max<int64_t>(tile_pos, (int64_t)g.TY * g.TZ);
-        tile_lds = std::max(tile_lds, align_resident_lds(la, g.TY, g.TZ));
-        cells += (int64_t)align_tiled_face_cells(la, lb, lc, pl.tymax, pl.tzmax);
-      } else {
-        mla = std::max(mla, la), mlb = std::max(mlb, lb), mlc = std::max(mlc, lc);
-      }
-    }
-    h_off[3 * m] = pos;
-    if ((size_t)cells * sizeof(uint4) > max_face) return TSA_EINTERNAL;
-    int32_t *d_scores = d_res, *d_final7 = d_res + m, *d_info = d_res + 8 * (size_t)m;
-    const int64_t *d_off = d_meta, *d_tboff = d_meta + 3 * (size_t)m + 1, *d_faceoff = d_tboff + m;
-    if (hipMemcpyAsync(d_seqs, h_seqs.data(), (size_t)pos, hipMemcpyHostToDevice, B.s) != hipSuccess ||
-        hipMemcpyAsync(d_meta, h_meta.data(), sizeof(int64_t) * (5 * (size_t)m + 1), hipMemcpyHostToDevice, B.s) !=
-            hipSuccess)
-      return TSA_EDEVICE;
-    if (mr && (rc = align_launch_resident(d_seqs, d_off, mr, max_pos, lds, kp, d_scores, d_final7, d_tb, d_tboff, B.s)))
-      return rc;
-    if (m > mr && tiled) {
-      if ((rc = align_launch_tiled(d_seqs, d_off + 3 * (size_t)mr, m - mr, pl.tymax, pl.tzmax, tile_pos, tile_lds, kp,
-                                   d_scores + mr, d_final7 + (size_t)NSTATE * mr, d_tb, d_tboff + mr, d_faces,
-                                   d_faceoff + mr, B.s)))
-        return rc;
-    } else if (m > mr) {
-      const int32_t mp = m - mr;
-      const size_t ws_bytes = plane_workspace_bytes(mp, mla, mlb, mlc);
-      if ((rc = plane_launch_batch(d_seqs, d_off + 3 * (size_t)mr, mp, mla, mlb, mlc, kp, d_scores + mr,
-                                   d_final7 + (size_t)NSTATE * mr, d_ws, ws_bytes, B.s, d_tb, d_tboff + mr)))
-        return rc;
-    }
-    hipLaunchKernelGGL(tb_walk_batch, dim3((m + 63) / 64), dim3(64), 0, B.s, d_tb, d_tboff, d_off, m, d_final7, d_moves,
-                       d_info);
-    if (hipGetLastError() != hipSuccess ||
-        hipMemcpyAsync(h_res.data(), d_res, sizeof(int32_t) * 12 * (size_t)m, hipMemcpyDeviceToHost, B.s) !=
-            hipSuccess ||
-        hipMemcpyAsync(h_moves.data(), d_moves, (size_t)pos, hipMemcpyDeviceToHost, B.s) != hipSuccess ||
-        hipStreamSynchronize(B.s) != hipSuccess)
-      return TSA_EDEVICE;
-    for (int32_t j = 0; j < m; ++j) {
-      const int32_t i = order[j];
-      const int32_t *info = h_res.data() + 8 * (size_t)m + 4 * (size_t)j;
-      const int64_t len = offsets[3 * (int64_t)i + 3] - offsets[3 * (int64_t)i];
-      if (info[0] < 1 || info[0] > len) return TSA_EINTERNAL;
-      std::memcpy(moves + (offsets[3 * (int64_t)i] - offsets[0]), h_moves.data() + h_off[3 * j], (size_t)info[0]);
-      scores[i] = h_res[j];
-      n_moves[i] = info[0];
-      starts[3 * (int64_t)i] = info[1], starts[3 * (int64_t)i + 1] = info[2], starts[3 * (int64_t)i + 2] = info[3];
-    }
-    i0 = i1;
-  }
-  return TSA_OK;
 }
 
 // tsa_describe_plan's suffix while plan overrides are set: " overrides=..."

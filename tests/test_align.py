@@ -92,6 +92,33 @@ def test_gpu_align_random(gpu, orc, kw):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("kw", [dict(), dict(score_bits=6), dict(score_bits=9)])
+def test_gpu_align_single_ignores_align_overrides(gpu, orc, kw):
+    """tsa_align_gpu takes the plane sweep on a host path of its own, whatever
+    align_mode, align_tile and align_tb_bytes say (a property any folding of it
+    into the batch path must keep): the oracle's score, start and moves, no
+    counted launch, and no cube budget -- the budget that fails tsa_align_batch
+    does not fail it. The default parameters, test_gpu_align_random's wrapping
+    set (6 bits) and a 9-bit one."""
+    rng = np.random.default_rng(52 + len(kw))
+    p, op = gpu.TsaParams.default(**kw), orc.default_params(**kw)
+    for la, lb, lc in ((5, 6, 7), (9, 64, 64)):
+        a, b, c = (rng.integers(0, 5, n).astype(np.uint8) for n in (la, lb, lc))
+        ref = orc.align(a, b, c, op)
+        before = gpu.kernel_launch_count()
+        for ov in (dict(), dict(align_mode="resident"), dict(align_mode="tiled", align_tile="3x4"),
+                   dict(align_tb_bytes=16)):
+            with gpu.overrides(**ov):
+                got = gpu.align(a, b, c, p)
+            assert got[0] == ref[0] and tuple(got[1]) == tuple(ref[1]) and np.array_equal(got[2], ref[2]), (la, lb, lc, ov)
+            assert gpu.kernel_launch_count() == before, (la, lb, lc, ov)
+        with gpu.overrides(align_tb_bytes=16):
+            with pytest.raises(gpu.TsaError) as e:
+                gpu.align_batch([(a, b, c)], p)
+            assert e.value.rc == gpu.TSA_ENOMEM
+
+
+@pytest.mark.gpu
 def test_gpu_align_256_cube(gpu, orc, synth):
     # configs[2] size: the pointer cube is 4*256*511*256 B = 134 MB of HBM; the
     # path must re-score to the kernel's score (12-bit wrap cannot occur here)

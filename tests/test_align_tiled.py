@@ -146,6 +146,24 @@ def test_tiled_schedule_emulated_all_a(orc):
             assert s == 3 * n and st == (0, 0, 0) and list(mv) == [0] * n, (n, tile)
 
 
+@pytest.mark.parametrize("kw", [dict(), dict(match=3, mismatch=-1, go=2, ge=2, sop=True, bits=6)])
+def test_tiled_emu_of_one_tile_is_the_resident_emu(kw):
+    """Both replays run the one step of tools/align_emu.py. With a tile cap of
+    at least (lb, lc) the tiled schedule is one tile with no face -- steps from
+    q = 1 -- and must give the resident schedule's (q from 2) score, final
+    states and pointer word of every cell."""
+    import align_emu
+    import align_tiled_emu
+    rng = np.random.default_rng(21)
+    for (la, lb, lc), tile in (((1, 1, 1), (1, 1)), ((7, 1, 5), (1, 5)), ((6, 9, 4), (64, 48))):
+        a, b, c = _rand_triple(rng, la, lb, lc)
+        res = align_emu.emulate(a, b, c, **kw)
+        til = align_tiled_emu.emulate(a, b, c, tile=tile, **kw)
+        assert align_tiled_emu.tile_geom(lb, lc, *tile)[2:] == (1, 1)
+        assert len(res[2]) == la * lb * lc
+        assert til == res, (kw, la, lb, lc)
+
+
 def test_tiled_emu_geometry_is_the_library_s(tsa):
     """The replay's tile grid is the one tsa_describe_align_plan reports."""
     import align_tiled_emu

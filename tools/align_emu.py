@@ -38,6 +38,7 @@ from literal_emu import penalties
 DX = (1, 1, 0, 0, 1, 0, 1)   # predecessor offsets per state (MOVE_CONSUMES)
 DY = (1, 0, 1, 0, 1, 1, 0)
 DZ = (1, 0, 0, 1, 0, 1, 1)
+ZERO = (0,) * 7
 
 
 def _wrap(v, bits):
@@ -47,60 +48,79 @@ def _wrap(v, bits):
     return ((v + (m >> 1)) % m) - (m >> 1)
 
 
-def emulate(a, b, c, match=1, mismatch=-1, go=2, ge=1, sop=False, bits=12):
-    """(score, final7, ptr) by the resident schedule; ptr maps a cell
-    (x, y, z) to its pointer word."""
-    a, b, c = (np.asarray(s, np.int64) & 3 for s in (a, b, c))
-    la, lb, lc = len(a), len(b), len(c)
-    Pen = penalties(go, ge)
-    w = lambda v: _wrap(int(v), bits)
-    mt, mm = w(match), w(mismatch)
-    s3_eq, s3_ab, s3_ne = w(3 * match), w(2 * (match + mismatch)), w(3 * mismatch)
-    zero = (0,) * 7
-    buf = [[[zero] * (lc + 1) for _ in range(lb + 1)] for _ in range(2)]
-    hist = {(y, z): dict(XY=(0, 0), YZ=(0, 0), XZ=(0, 0), M3=(0, 0), M2=(0, 0))
-            for y in range(1, lb + 1) for z in range(1, lc + 1)}
-    ptr, fin = {}, None
+class Cell:
+    """The literal cell of one triple under one parameter set: the score
+    constants, MAX7 and the step of one position, shared by the resident and the
+    tiled replay (csrc/align_step.h is what the two kernels share)."""
 
-    def max7(T, pred, add):
+    def __init__(self, a, b, c, match=1, mismatch=-1, go=2, ge=1, sop=False, bits=12):
+        self.a, self.b, self.c = (np.asarray(s, np.int64) & 3 for s in (a, b, c))
+        self.la, self.lb, self.lc = len(self.a), len(self.b), len(self.c)
+        self.pen, self.sop = penalties(go, ge), sop
+        self.w = w = lambda v: _wrap(int(v), bits)
+        self.mt, self.mm = w(match), w(mismatch)
+        self.s3 = w(3 * match), w(2 * (match + mismatch)), w(3 * mismatch)
+
+    def max7(self, T, pred, add):
         best, arg = None, 0
         for s in range(7):
-            v = w(pred[s] - int(Pen[T][s]) + add)
+            v = self.w(pred[s] - int(self.pen[T][s]) + add)
             if best is None or v > best:
                 best, arg = v, s
         return best, arg
 
-    def adds(x, y, z):
+    def adds(self, x, y, z):
         """(sab, sbc, sac, s3) of cell (x, y, z); x clamped into A as the kernel's lookup."""
-        ax, by, cz = int(a[min(max(x, 1), la) - 1]), int(b[y - 1]), int(c[z - 1])
-        sab = mt if ax == by else mm
-        sbc = mt if by == cz else mm
-        sac = mt if ax == cz else mm
-        if sop:
-            s3 = w(sab + sbc + sac)
+        ax, by, cz = int(self.a[min(max(x, 1), self.la) - 1]), int(self.b[y - 1]), int(self.c[z - 1])
+        sab = self.mt if ax == by else self.mm
+        sbc = self.mt if by == cz else self.mm
+        sac = self.mt if ax == cz else self.mm
+        if self.sop:
+            s3 = self.w(sab + sbc + sac)
         else:
-            s3 = (s3_eq if by == cz else s3_ab) if ax == by else s3_ne
+            s3 = (self.s3[0] if by == cz else self.s3[1]) if ax == by else self.s3[2]
         return sab, sbc, sac, s3
 
+    @staticmethod
+    def history():
+        return dict(XY=(0, 0), YZ=(0, 0), XZ=(0, 0), M3=(0, 0), M2=(0, 0))
+
+    def step(self, h, x, own, n1, w1, nw1, y, z):
+        """One step of the position at global (y, z), 0 <= x <= la, on its four
+        reads: updates its history h and returns (cell, pointer word), None
+        at x = 0, where there is no cell."""
+        out = None
+        if x == 0:
+            h["M3"] = self.max7(0, ZERO, self.adds(1, y, z)[3])
+        else:
+            res = [h["M3"], self.max7(1, own, 0), self.max7(2, n1, 0), self.max7(3, w1, 0), h["XY"], h["YZ"], h["XZ"]]
+            out = tuple(v for v, _ in res), sum(g << (3 * T) for T, (_, g) in enumerate(res))
+            h["M3"] = h["M2"]
+        sab, sbc, sac, _ = self.adds(x + 1, y, z)
+        h["XY"], h["XZ"], h["YZ"] = self.max7(4, n1, sab), self.max7(6, w1, sac), self.max7(5, nw1, sbc)
+        h["M2"] = self.max7(0, nw1, self.adds(x + 2, y, z)[3])
+        return out
+
+
+def emulate(a, b, c, match=1, mismatch=-1, go=2, ge=1, sop=False, bits=12):
+    """(score, final7, ptr) by the resident schedule; ptr maps a cell
+    (x, y, z) to its pointer word."""
+    K = Cell(a, b, c, match, mismatch, go, ge, sop, bits)
+    la, lb, lc = K.la, K.lb, K.lc
+    buf = [[[ZERO] * (lc + 1) for _ in range(lb + 1)] for _ in range(2)]
+    hist = {(y, z): K.history() for y in range(1, lb + 1) for z in range(1, lc + 1)}
+    ptr, fin = {}, None
     for q in range(2, la + lb + lc + 1):
         rd, wr = buf[(q - 1) & 1], buf[q & 1]
         for (y, z), h in hist.items():
             x = q - y - z
             if x < 0 or x > la:
                 continue
-            own, n1, w1, nw1 = rd[y][z], rd[y - 1][z], rd[y][z - 1], rd[y - 1][z - 1]
-            if x == 0:
-                h["M3"] = max7(0, zero, adds(1, y, z)[3])
-            else:
-                res = [h["M3"], max7(1, own, 0), max7(2, n1, 0), max7(3, w1, 0), h["XY"], h["YZ"], h["XZ"]]
-                wr[y][z] = tuple(v for v, _ in res)
-                ptr[(x, y, z)] = sum(g << (3 * T) for T, (_, g) in enumerate(res))
+            out = K.step(h, x, rd[y][z], rd[y - 1][z], rd[y][z - 1], rd[y - 1][z - 1], y, z)
+            if out:
+                wr[y][z], ptr[(x, y, z)] = out
                 if (x, y, z) == (la, lb, lc):
                     fin = wr[y][z]
-                h["M3"] = h["M2"]
-            sab, sbc, sac, _ = adds(x + 1, y, z)
-            h["XY"], h["XZ"], h["YZ"] = max7(4, n1, sab), max7(6, w1, sac), max7(5, nw1, sbc)
-            h["M2"] = max7(0, nw1, adds(x + 2, y, z)[3])
     return max(fin), fin, ptr
 
 

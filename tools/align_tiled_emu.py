@@ -31,10 +31,7 @@ as a wrong move or score.
 """
 from __future__ import annotations
 
-import numpy as np
-
-from align_emu import _wrap, walk
-from literal_emu import penalties
+from align_emu import ZERO, Cell, walk
 
 POISON = tuple(12345 - 1111 * s for s in range(7))
 
@@ -48,48 +45,21 @@ def tile_geom(lb, lc, tymax, tzmax):
 def emulate(a, b, c, match=1, mismatch=-1, go=2, ge=1, sop=False, bits=12, tile=(64, 48)):
     """(score, final7, ptr) by the tiled schedule; ptr maps a cell (x, y, z)
     in global coordinates to its pointer word."""
-    a, b, c = (np.asarray(s, np.int64) & 3 for s in (a, b, c))
-    la, lb, lc = len(a), len(b), len(c)
+    K = Cell(a, b, c, match, mismatch, go, ge, sop, bits)
+    la, lb, lc = K.la, K.lb, K.lc
     TY, TZ, nty, ntz = tile_geom(lb, lc, *tile)
-    Pen = penalties(go, ge)
-    w = lambda v: _wrap(int(v), bits)
-    mt, mm = w(match), w(mismatch)
-    s3_eq, s3_ab, s3_ne = w(3 * match), w(2 * (match + mismatch)), w(3 * mismatch)
-    zero = (0,) * 7
     buf = [[[POISON] * (TZ + 1) for _ in range(TY + 1)] for _ in range(2)]
     yface = [[[POISON] * (lc + 1) for _ in range(la + 1)] for _ in range(2)]   # [parity][x][global z]
     zface = [[[POISON] * (TY + 1) for _ in range(la + 1)] for _ in range(2)]   # [parity][x][local y]
     ptr, fin = {}, None
-
-    def max7(T, pred, add):
-        best, arg = None, 0
-        for s in range(7):
-            v = w(pred[s] - int(Pen[T][s]) + add)
-            if best is None or v > best:
-                best, arg = v, s
-        return best, arg
-
-    def adds(x, gy, gz):
-        """(sab, sbc, sac, s3) of cell (x, gy, gz); x clamped into A as the kernel's lookup."""
-        ax, by, cz = int(a[min(max(x, 1), la) - 1]), int(b[gy - 1]), int(c[gz - 1])
-        sab = mt if ax == by else mm
-        sbc = mt if by == cz else mm
-        sac = mt if ax == cz else mm
-        if sop:
-            s3 = w(sab + sbc + sac)
-        else:
-            s3 = (s3_eq if by == cz else s3_ab) if ax == by else s3_ne
-        return sab, sbc, sac, s3
-
     for ty in range(nty):
         for tz in range(ntz):
             y0, z0 = ty * TY, tz * TZ
             tyl, tzl = min(TY, lb - y0), min(TZ, lc - z0)
             for p in range(2):                                   # zeroed again, whatever the last tile left
                 for y in range(TY + 1):
-                    buf[p][y] = [zero] * (TZ + 1)
-            hist = {(y, z): dict(XY=(0, 0), YZ=(0, 0), XZ=(0, 0), M3=(0, 0), M2=(0, 0))
-                    for y in range(1, tyl + 1) for z in range(1, tzl + 1)}
+                    buf[p][y] = [ZERO] * (TZ + 1)
+            hist = {(y, z): K.history() for y in range(1, tyl + 1) for z in range(1, tzl + 1)}
             yrd = yface[(ty - 1) & 1] if ty else None
             zrd = zface[(tz - 1) & 1] if tz else None
             ywr = yface[ty & 1] if ty + 1 < nty else None
@@ -108,20 +78,11 @@ def emulate(a, b, c, match=1, mismatch=-1, go=2, ge=1, sop=False, bits=12, tile=
                     x = q - y - z
                     if x < 0 or x > la:
                         continue
-                    gy, gz = y0 + y, z0 + z
-                    own, n1, w1, nw1 = rd[y][z], rd[y - 1][z], rd[y][z - 1], rd[y - 1][z - 1]
-                    if x == 0:
-                        h["M3"] = max7(0, zero, adds(1, gy, gz)[3])
-                    else:
-                        res = [h["M3"], max7(1, own, 0), max7(2, n1, 0), max7(3, w1, 0), h["XY"], h["YZ"], h["XZ"]]
-                        new[(y, z)] = tuple(v for v, _ in res)
-                        ptr[(x, gy, gz)] = sum(g << (3 * T) for T, (_, g) in enumerate(res))
-                        if (x, gy, gz) == (la, lb, lc):
+                    out = K.step(h, x, rd[y][z], rd[y - 1][z], rd[y][z - 1], rd[y - 1][z - 1], y0 + y, z0 + z)
+                    if out:
+                        new[(y, z)], ptr[(x, y0 + y, z0 + z)] = out
+                        if (x, y0 + y, z0 + z) == (la, lb, lc):
                             fin = new[(y, z)]
-                        h["M3"] = h["M2"]
-                    sab, sbc, sac, _ = adds(x + 1, gy, gz)
-                    h["XY"], h["XZ"], h["YZ"] = max7(4, n1, sab), max7(6, w1, sac), max7(5, nw1, sbc)
-                    h["M2"] = max7(0, nw1, adds(x + 2, gy, gz)[3])
                 for f in range(tzl + tyl + 1):                   # the face threads
                     row = f <= tzl
                     y, z = (0, f) if row else (f - tzl, 0)
