@@ -213,7 +213,9 @@ def test_gpu_align_tiled_real_tile_sizes(gpu, orc):
     """One batch under the default tile, caller order kept: the smallest shapes
     that cross it (1 x 2, 2 x 2 and 3 x 3 grids, a single row of 86 tiles, a
     single column of 65, LA beyond lb + lc), mixed with triples that stay
-    resident."""
+    resident. The sequences are independent random ones, so the optimal paths
+    are short and stay in one tile -- only (40,129,129) crosses a y and a z
+    seam; paths across seams and tile corners are test_align_paths.py's."""
     rng = np.random.default_rng(43)
     trips = [_rand_triple(rng, *s) for s in CROSS]
     with gpu.overrides(align_mode="tiled"):
