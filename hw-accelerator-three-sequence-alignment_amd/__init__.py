@@ -64,7 +64,7 @@ EXPORTS = (
     "tsa_device_count", "tsa_strerror", "tsa_version", "tsa_describe_plan", "tsa_align_gpu",
     "tsa_fallback_count", "tsa_check_fallback_count", "tsa_score_batch_async_p2", "tsa_pack2",
     "tsa_score_gpu_multi", "tsa_score_batch_devices", "tsa_set_override", "tsa_get_overrides",
-    "tsa_kernel_launch_count", "tsa_align_batch", "tsa_describe_align_plan",
+    "tsa_kernel_launch_count", "tsa_align_batch", "tsa_describe_align_plan", "tsa_align_batch_lowmem",
 )
 
 # Plan overrides the library accepts (tsa_set_override; include/trialign.h).
@@ -147,6 +147,7 @@ def _load_lib() -> ctypes.CDLL:
                                   pp, i32p, u8p, ctypes.c_int32, i32p, i32p, ctypes.c_int32]
     lib.tsa_align_batch.argtypes = [u8p, i64p, ctypes.c_int32, pp, i32p, u8p, i32p, i32p,
                                     ctypes.c_int32]
+    lib.tsa_align_batch_lowmem.argtypes = lib.tsa_align_batch.argtypes
     lib.tsa_score_gpu_multi.argtypes = [u8p, ctypes.c_int32, u8p, ctypes.c_int32, u8p,
                                         ctypes.c_int32, pp, i32p, ctypes.c_int32, i32p,
                                         ctypes.POINTER(ctypes.c_double)]
@@ -169,7 +170,8 @@ def _load_lib() -> ctypes.CDLL:
                  "tsa_batch_workspace_size", "tsa_score_batch_async", "tsa_device_count",
                  "tsa_describe_plan", "tsa_align_gpu", "tsa_score_batch_async_p2", "tsa_pack2",
                  "tsa_score_gpu_multi", "tsa_score_batch_devices", "tsa_set_override",
-                 "tsa_get_overrides", "tsa_align_batch", "tsa_describe_align_plan"):
+                 "tsa_get_overrides", "tsa_align_batch", "tsa_describe_align_plan",
+                 "tsa_align_batch_lowmem"):
         getattr(lib, name).restype = ctypes.c_int
     return lib
 
@@ -367,14 +369,19 @@ def align(a, b, c, params: Optional[TsaParams] = None, device: int = 0):
 
 
 def align_batch(triples=None, params: Optional[TsaParams] = None, device: int = 0,
-                seqs: Optional[np.ndarray] = None, offsets: Optional[np.ndarray] = None) -> list:
+                seqs: Optional[np.ndarray] = None, offsets: Optional[np.ndarray] = None,
+                lowmem: bool = False) -> list:
     """Optimal alignments of many triples in one call (tsa_align_batch): a
     list of ``(score, start, moves)``, one per triple in the caller's order,
     each as ``align`` returns it. Triples whose (y,z) planes fit a workgroup
     run the resident kernel, one launch per chunk of pointer cubes; larger
     ones the plane sweep or, under ``align_mode="tiled"``, the tiled resident
     kernel (``describe_align_plan``). The overrides ``align_mode``,
-    ``align_tile`` and ``align_tb_bytes`` steer path, tiling and chunking."""
+    ``align_tile`` and ``align_tb_bytes`` steer path, tiling and chunking.
+    ``lowmem=True`` calls tsa_align_batch_lowmem: the same results, the larger
+    triples by the strip path (``align_mode="strip"`` unless that override is
+    set), which keeps the pointers of one tile row of a cube at a time, so
+    cubes over the budget can be aligned, for up to twice the cell work."""
     p = params or TsaParams.default()
     if seqs is None:
         seqs, offsets = pack_batch(triples)
@@ -385,10 +392,11 @@ def align_batch(triples=None, params: Optional[TsaParams] = None, device: int = 
     nm = np.zeros(max(n, 1), dtype=np.int32)
     st = np.zeros(max(3 * n, 1), dtype=np.int32)
     mv = np.zeros(max(int(offsets[-1] - offsets[0]) if n else 0, 1), dtype=np.uint8)
-    rc = _lib.tsa_align_batch(_ptr(seqs, ctypes.c_uint8), _ptr(offsets, ctypes.c_int64), n,
-                              ctypes.byref(p), _ptr(sc, ctypes.c_int32), _ptr(mv, ctypes.c_uint8),
-                              _ptr(nm, ctypes.c_int32), _ptr(st, ctypes.c_int32), device)
-    _check(rc, "tsa_align_batch")
+    name = "tsa_align_batch_lowmem" if lowmem else "tsa_align_batch"
+    rc = getattr(_lib, name)(_ptr(seqs, ctypes.c_uint8), _ptr(offsets, ctypes.c_int64), n,
+                             ctypes.byref(p), _ptr(sc, ctypes.c_int32), _ptr(mv, ctypes.c_uint8),
+                             _ptr(nm, ctypes.c_int32), _ptr(st, ctypes.c_int32), device)
+    _check(rc, name)
     out = []
     for i in range(n):
         m0 = int(offsets[3 * i] - offsets[0])
@@ -537,8 +545,10 @@ def describe_plan(n: int, max_la: int, max_lb: int, max_lc: int,
 def describe_align_plan(n: int, la: int, lb: int, lc: int, params: Optional[TsaParams] = None) -> str:
     """The path a group of ``n`` triples of these lengths takes in
     ``align_batch`` under the current overrides (tsa_describe_align_plan;
-    host-only): ``resident ...``, ``tiled tile=TYxTZ tiles=NYxNZ ...`` or
-    ``plane``."""
+    host-only): ``resident ...``, ``tiled tile=TYxTZ tiles=NYxNZ ...``,
+    ``strip tile=TYxTZ tiles=NYxNZ lds=... cube=<strip cube bytes> faces=<face
+    bytes>`` (``align_mode="strip"``, what ``align_batch(lowmem=True)`` plans)
+    or ``plane``."""
     p = params or TsaParams.default()
     buf = ctypes.create_string_buffer(256)
     _check(_lib.tsa_describe_align_plan(n, la, lb, lc, ctypes.byref(p), buf, len(buf)), "tsa_describe_align_plan")

@@ -1,10 +1,10 @@
 // align_api.hip -- the traceback entry points of include/trialign.h:
-// tsa_align_batch, tsa_align_gpu (one triple, always the plane sweep) and
-// tsa_describe_align_plan. Host code only: which path a triple takes, the
-// chunks of pointer cubes, the device buffers and the launches of the resident
-// kernel (align_kernel.hip), the tiled resident kernel
-// (align_tiled_kernel.hip), the batched plane sweep and the batched walk
-// (plane_kernel.hip).
+// tsa_align_batch, tsa_align_batch_lowmem, tsa_align_gpu (one triple, always
+// the plane sweep) and tsa_describe_align_plan. Host code only: which path a
+// triple takes, the chunks of pointer cubes, the device buffers and the
+// launches of the resident kernel (align_kernel.hip), the tiled resident kernel
+// (align_tiled_kernel.hip), the strip kernel (align_strip_kernel.hip), the
+// batched plane sweep and the batched walks (plane_kernel.hip).
 //
 // Traceback is an extension: the reference's alignment-output ports are
 // commented out (src/TriAlign_tb.sv:239-260).
@@ -47,11 +47,15 @@ struct AlignBufs {
 // per triple, so it needs a group large enough to fill the device: without an
 // override, the over-capacity triples of a chunk are tiled when there are at
 // least kAlignTiledMinGroup of them (profiles/align_tiled.jsonl)
-// and take the plane sweep otherwise.
-enum AlignPath { ALIGN_RESIDENT, ALIGN_TILED, ALIGN_PLANE };
-enum AlignMode { ALIGN_MODE_AUTO, ALIGN_MODE_RESIDENT, ALIGN_MODE_PLANE, ALIGN_MODE_TILED };
+// and take the plane sweep otherwise. Under align_mode = strip (what
+// tsa_align_batch_lowmem plans by default) they take the strip path instead,
+// which keeps the pointers of one tile row of a cube at a time: never chosen
+// without being asked for, since it sweeps most cells twice.
+enum AlignPath { ALIGN_RESIDENT, ALIGN_TILED, ALIGN_PLANE, ALIGN_STRIP };
+enum AlignMode { ALIGN_MODE_AUTO, ALIGN_MODE_RESIDENT, ALIGN_MODE_PLANE, ALIGN_MODE_TILED, ALIGN_MODE_STRIP };
 struct AlignPlan {
   AlignMode mode = ALIGN_MODE_AUTO;
+  bool mode_set = false;  // align_mode is set
   bool capped = false;  // align_tile is set
   int32_t tymax = ALIGN_TILE_Y, tzmax = ALIGN_TILE_Z;
 };
@@ -69,7 +73,9 @@ int align_plan_read(AlignPlan *pl) {
     if (!strcmp(v, "resident")) pl->mode = ALIGN_MODE_RESIDENT;
     else if (!strcmp(v, "plane")) pl->mode = ALIGN_MODE_PLANE;
     else if (!strcmp(v, "tiled")) pl->mode = ALIGN_MODE_TILED;
+    else if (!strcmp(v, "strip")) pl->mode = ALIGN_MODE_STRIP;
     else return TSA_EINVAL;
+    pl->mode_set = true;
   }
   if (override_str("align_tile", v, sizeof v)) {  // "TYxTZ", decimal digits only
     long e[2] = {0, 0};
@@ -89,16 +95,18 @@ int align_plan_read(AlignPlan *pl) {
 }
 
 // Over capacity: the triple does not go to the resident kernel as a whole.
-// With align_tile set under align_mode = tiled that is any triple larger than
-// the tile (tests put tiny cubes through many tiles that way).
+// With align_tile set under align_mode = tiled or strip that is any triple
+// larger than the tile (tests put tiny cubes through many tiles that way).
 bool align_over(const AlignPlan &pl, int32_t la, int32_t lb, int32_t lc) {
-  if (pl.mode == ALIGN_MODE_TILED && pl.capped) return lb > pl.tymax || lc > pl.tzmax;
+  if ((pl.mode == ALIGN_MODE_TILED || pl.mode == ALIGN_MODE_STRIP) && pl.capped)
+    return lb > pl.tymax || lc > pl.tzmax;
   return !align_resident_fits(la, lb, lc);
 }
 
 // The path of the over-capacity triples of a group that holds n_over of them.
 AlignPath align_over_path(const AlignPlan &pl, int32_t n_over) {
   if (pl.mode == ALIGN_MODE_TILED) return ALIGN_TILED;
+  if (pl.mode == ALIGN_MODE_STRIP) return ALIGN_STRIP;
   if (pl.mode == ALIGN_MODE_AUTO && n_over >= kAlignTiledMinGroup) return ALIGN_TILED;
   return ALIGN_PLANE;
 }
@@ -113,18 +121,21 @@ AlignPath align_path(const AlignPlan &pl, int32_t la, int32_t lb, int32_t lc, in
 // buffers, the chunks and the launches all read these numbers.
 struct AlignTriple {
   int32_t la, lb, lc;
-  bool over;     // not the resident kernel's: tiled or plane, as its chunk decides
-  size_t cube;   // bytes of its pointer cube
-  size_t face;   // 16-byte cells of its face workspace if the chunk is tiled
+  bool over;     // not the resident kernel's: tiled or plane, as its chunk decides, or strip
+  size_t cube;   // bytes of its pointer cube; of its strip cube on the strip path
+  size_t face;   // 16-byte cells of its face workspace if the chunk is tiled or strips
+  size_t need;   // what it takes of the budget: the cube; with the faces on the strip path, where they are O(N^3/TY)
+  int32_t nty;   // its strips on the strip path
   int64_t pos;   // positions of its workgroup: lb*lc, or TY*TZ of an over-capacity triple's tiles
   size_t lds;    // align_resident_lds of that plane or tile
 };
-// Consecutive triples [i0, i1) whose cubes fit the budget together, as a batch
+// Consecutive triples [i0, i1) whose needs fit the budget together, as a batch
 // of its own: what its launches and the buffers need.
 struct AlignChunk {
   int32_t i0, i1, n_over = 0;
-  bool tiled = false;                     // the path of the n_over over-capacity triples
-  size_t cube = 0, seq = 0;               // bytes of the cubes and of the sequences
+  bool tiled = false, strip = false;      // the path of the n_over over-capacity triples
+  int32_t max_nty = 0;                    // the strip launches: the most strips of a triple
+  size_t need = 0, cube = 0, seq = 0;     // bytes against the budget, of the cubes and of the sequences
   int64_t max_pos = 1, tile_pos = 1;      // the resident and the tiled launch
   size_t lds = 0, tile_lds = 0, face = 0; // face: bytes
   int32_t mla = 1, mlb = 1, mlc = 1;      // the plane sweep
@@ -141,9 +152,14 @@ int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KPar
     AlignTriple &t = T[i];
     t.la = (int32_t)(o[1] - o[0]), t.lb = (int32_t)(o[2] - o[1]), t.lc = (int32_t)(o[3] - o[2]);
     t.over = align_path(pl, t.la, t.lb, t.lc, 0) != ALIGN_RESIDENT;
-    t.cube = tb_cube_bytes(t.la, t.lb, t.lc);
+    const bool strip = t.over && pl.mode == ALIGN_MODE_STRIP;
+    t.cube = strip ? align_strip_cube_bytes(t.la, t.lb, t.lc, pl.tymax, pl.tzmax) : tb_cube_bytes(t.la, t.lb, t.lc);
     const AlignTileGeom g = t.over ? align_tile_geom(t.lb, t.lc, pl.tymax, pl.tzmax) : AlignTileGeom{t.lb, t.lc, 1, 1};
-    t.face = t.over ? align_tiled_face_cells(t.la, t.lb, t.lc, pl.tymax, pl.tzmax) : 0;
+    t.face = strip    ? align_strip_face_cells(t.la, t.lb, t.lc, pl.tymax, pl.tzmax)
+             : t.over ? align_tiled_face_cells(t.la, t.lb, t.lc, pl.tymax, pl.tzmax)
+                      : 0;
+    t.need = t.cube + (strip ? sizeof(uint4) * t.face : 0);
+    t.nty = g.nty;
     t.pos = (int64_t)g.TY * g.TZ;
     t.lds = align_resident_lds(t.la, g.TY, g.TZ);
   }
@@ -155,8 +171,9 @@ int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KPar
     int32_t j = i;
     for (; j < n && j - i < 65535; ++j) {
       const AlignTriple &t = T[j];
-      if (t.cube > budget) return TSA_ENOMEM;  // one cube over the budget, as a failed allocation
-      if (t.cube > budget - c.cube) break;
+      if (t.need > budget) return TSA_ENOMEM;  // one triple over the budget, as a failed allocation
+      if (t.need > budget - c.need) break;
+      c.need += t.need;
       c.cube += t.cube;
       c.seq += (size_t)t.la + t.lb + t.lc;
       if (!t.over) {
@@ -166,11 +183,13 @@ int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KPar
       ++c.n_over;
       c.tile_pos = std::max(c.tile_pos, t.pos), c.tile_lds = std::max(c.tile_lds, t.lds);
       c.face += sizeof(uint4) * t.face;
+      c.max_nty = std::max(c.max_nty, t.nty);
       c.mla = std::max(c.mla, t.la), c.mlb = std::max(c.mlb, t.lb), c.mlc = std::max(c.mlc, t.lc);
     }
     c.i0 = i, c.i1 = j;
     c.tiled = c.n_over && align_over_path(pl, c.n_over) == ALIGN_TILED;
-    if (!c.tiled) c.face = 0, c.ws = c.n_over ? plane_workspace_bytes(c.n_over, c.mla, c.mlb, c.mlc) : 0;
+    c.strip = c.n_over && align_over_path(pl, c.n_over) == ALIGN_STRIP;
+    if (!c.tiled && !c.strip) c.face = 0, c.ws = c.n_over ? plane_workspace_bytes(c.n_over, c.mla, c.mlb, c.mlc) : 0;
     chunks.push_back(c);
     max_cube = std::max(max_cube, c.cube), max_seq = std::max(max_seq, c.seq);
     max_ws = std::max(max_ws, c.ws), max_face = std::max(max_face, c.face);
@@ -184,18 +203,20 @@ int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KPar
   int32_t *d_res = nullptr;   // m scores, 7m final states, 4m walk infos
   uint32_t *d_tb = nullptr;
   void *d_ws = nullptr, *d_faces = nullptr;
+  int32_t *d_walk = nullptr;  // the walker records of a chunk's strip triples
   if (hipStreamCreateWithFlags(&B.s, hipStreamNonBlocking) != hipSuccess) return TSA_EDEVICE;
   if (!B.alloc(&d_seqs, max_seq) || !B.alloc(&d_moves, max_seq) ||
       !B.alloc(&d_meta, sizeof(int64_t) * (5 * (size_t)max_n + 1)) ||
       !B.alloc(&d_res, sizeof(int32_t) * 12 * (size_t)max_n) || !B.alloc(&d_tb, max_cube) ||
-      !B.alloc(&d_ws, max_ws) || !B.alloc(&d_faces, max_face))
+      !B.alloc(&d_ws, max_ws) || !B.alloc(&d_faces, max_face) ||
+      !B.alloc(&d_walk, pl.mode == ALIGN_MODE_STRIP ? sizeof(int32_t) * ALIGN_WALK_REC * (size_t)max_n : 0))
     return TSA_ENOMEM;
   std::vector<uint8_t> h_seqs(max_seq), h_moves(max_seq);
   std::vector<int64_t> h_meta(5 * (size_t)max_n + 1);
   std::vector<int32_t> h_res(12 * (size_t)max_n), order((size_t)max_n);
   for (const AlignChunk &c : chunks) {
-    // resident triples first, then the over-capacity ones (tiled or plane, one
-    // path for all of a chunk), packed back to back, so each path sees a
+    // resident triples first, then the over-capacity ones (tiled, plane or strip,
+    // one path for all of a chunk), packed back to back, so each path sees a
     // contiguous sub-batch
     const int32_t m = c.i1 - c.i0, mr = m - c.n_over;
     int32_t r = 0, v = mr;
@@ -210,7 +231,7 @@ int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KPar
       h_tboff[j] = word;
       word += (int64_t)(t.cube / sizeof(uint32_t));
       h_faceoff[j] = cells;
-      if (c.tiled) cells += (int64_t)t.face;
+      if (c.tiled || c.strip) cells += (int64_t)t.face;
     }
     h_off[3 * m] = pos;
     int32_t *d_scores = d_res, *d_final7 = d_res + m, *d_info = d_res + 8 * (size_t)m;
@@ -227,12 +248,29 @@ int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KPar
       rc = align_launch_tiled(d_seqs, d_off + 3 * (size_t)mr, c.n_over, pl.tymax, pl.tzmax, c.tile_pos, c.tile_lds, kp,
                               d_scores + mr, d_final7 + (size_t)NSTATE * mr, d_tb, d_tboff + mr, d_faces,
                               d_faceoff + mr, B.s);
-    else if (c.n_over)
+    else if (c.n_over && !c.strip)
       rc = plane_launch_batch(d_seqs, d_off + 3 * (size_t)mr, c.n_over, c.mla, c.mlb, c.mlc, kp, d_scores + mr,
                               d_final7 + (size_t)NSTATE * mr, d_ws, c.ws, B.s, d_tb, d_tboff + mr);
     if (rc) return rc;
-    hipLaunchKernelGGL(tb_walk_batch, dim3((m + 63) / 64), dim3(64), 0, B.s, d_tb, d_tboff, d_off, m, d_final7, d_moves,
-                       d_info);
+    // the strip triples are walked strip by strip below; every other one has its whole cube
+    const int32_t mw = c.strip ? mr : m;
+    if (mw)
+      hipLaunchKernelGGL(tb_walk_batch, dim3((mw + 63) / 64), dim3(64), 0, B.s, d_tb, d_tboff, d_off, mw, d_final7,
+                         d_moves, d_info);
+    if (c.strip) {
+      // forward: the y faces of every strip but the last; then the strips, last
+      // to first, each followed by the walk of its pointers. j < 0: the forward form.
+      for (int32_t j = c.max_nty >= 2 ? -1 : 0; j < c.max_nty; ++j) {
+        if ((rc = align_launch_strip(d_seqs, d_off + 3 * (size_t)mr, c.n_over, pl.tymax, pl.tzmax, c.tile_pos,
+                                     c.tile_lds, kp, j, d_walk, d_scores + mr, d_final7 + (size_t)NSTATE * mr, d_tb,
+                                     d_tboff + mr, d_faces, d_faceoff + mr, B.s)))
+          return rc;
+        if (j >= 0)
+          hipLaunchKernelGGL(tb_walk_strip, dim3((c.n_over + 63) / 64), dim3(64), 0, B.s, d_tb, d_tboff + mr,
+                             d_off + 3 * (size_t)mr, c.n_over, pl.tymax, pl.tzmax, j, d_final7 + (size_t)NSTATE * mr,
+                             d_walk, d_moves, d_info + 4 * (size_t)mr);
+      }
+    }
     if (hipGetLastError() != hipSuccess ||
         hipMemcpyAsync(h_res.data(), d_res, sizeof(int32_t) * 12 * (size_t)m, hipMemcpyDeviceToHost, B.s) !=
             hipSuccess ||
@@ -272,14 +310,26 @@ int tsa_describe_align_plan(int32_t n, int32_t la, int32_t lb, int32_t lc, const
                align_resident_lds(la, g.TY, g.TZ), 16 * align_tiled_face_cells(la, lb, lc, pl.tymax, pl.tzmax));
       break;
     }
+    case ALIGN_STRIP: {
+      const AlignTileGeom g = align_tile_geom(lb, lc, pl.tymax, pl.tzmax);
+      snprintf(buf, len, "strip tile=%dx%d tiles=%dx%d lds=%zu cube=%zu faces=%zu", g.TY, g.TZ, g.nty, g.ntz,
+               align_resident_lds(la, g.TY, g.TZ), align_strip_cube_bytes(la, lb, lc, pl.tymax, pl.tzmax),
+               16 * align_strip_face_cells(la, lb, lc, pl.tymax, pl.tzmax));
+      break;
+    }
     default:
       snprintf(buf, len, "plane");
   }
   return TSA_OK;
 }
 
-int tsa_align_batch(const uint8_t *seqs, const int64_t *offsets, int32_t n, const tsa_params *p,
-                    int32_t *scores, uint8_t *moves, int32_t *n_moves, int32_t *starts, int32_t device) {
+}  // extern "C"
+
+namespace {
+// tsa_align_batch and tsa_align_batch_lowmem: validation, plan, budget, run.
+// lowmem: the plan mode is strip unless align_mode is set.
+int align_batch_entry(const uint8_t *seqs, const int64_t *offsets, int32_t n, const tsa_params *p, int32_t *scores,
+                      uint8_t *moves, int32_t *n_moves, int32_t *starts, int32_t device, bool lowmem) {
   if (!seqs || !offsets || !scores || !moves || !n_moves || !starts || n < 0 || !params_ok(p)) return TSA_EINVAL;
   for (int32_t i = 0; i < n; ++i) {
     const int64_t *o = offsets + 3 * (int64_t)i;
@@ -297,11 +347,13 @@ int tsa_align_batch(const uint8_t *seqs, const int64_t *offsets, int32_t n, cons
   if (rc) return rc;
   AlignPlan pl;
   if ((rc = align_plan_read(&pl))) return rc;
+  if (lowmem && !pl.mode_set) pl.mode = ALIGN_MODE_STRIP;
   if (hipSetDevice(device) != hipSuccess) return TSA_EDEVICE;
   // The pointer-cube budget of a chunk: align_tb_bytes, or half of the device
   // memory free at the call (the other half is left to the caller's own
   // buffers and to the sequences, moves, plane rings and tile faces of the
-  // chunk, all of which are O(N^2) against the cubes' O(N^3)).
+  // chunk, all of which are O(N^2) against the cubes' O(N^3)). On the strip
+  // path a triple counts with its strip cube and its kept faces.
   size_t budget = 0;
   long ov = 0;
   if (override_int("align_tb_bytes", &ov)) {
@@ -313,6 +365,19 @@ int tsa_align_batch(const uint8_t *seqs, const int64_t *offsets, int32_t n, cons
     budget = free_b / 2;
   }
   return align_run(seqs, offsets, n, kp, pl, budget, scores, moves, n_moves, starts);
+}
+}  // namespace
+
+extern "C" {
+
+int tsa_align_batch(const uint8_t *seqs, const int64_t *offsets, int32_t n, const tsa_params *p,
+                    int32_t *scores, uint8_t *moves, int32_t *n_moves, int32_t *starts, int32_t device) {
+  return align_batch_entry(seqs, offsets, n, p, scores, moves, n_moves, starts, device, false);
+}
+
+int tsa_align_batch_lowmem(const uint8_t *seqs, const int64_t *offsets, int32_t n, const tsa_params *p,
+                           int32_t *scores, uint8_t *moves, int32_t *n_moves, int32_t *starts, int32_t device) {
+  return align_batch_entry(seqs, offsets, n, p, scores, moves, n_moves, starts, device, true);
 }
 
 // One triple, always by the plane sweep, with buffers and a one-thread walk of

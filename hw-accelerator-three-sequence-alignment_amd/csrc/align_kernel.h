@@ -1,7 +1,7 @@
 // align_kernel.h -- what the traceback entry points (align_api.hip) launch: the
 // resident kernel (align_kernel.hip), the tiled resident kernel
-// (align_tiled_kernel.hip), the batch form of the TB plane sweep and the
-// batched walk (plane_kernel.hip).
+// (align_tiled_kernel.hip), the strip kernel (align_strip_kernel.hip), the
+// batch form of the TB plane sweep and the batched walks (plane_kernel.hip).
 #pragma once
 
 #include "tsa_internal.h"
@@ -73,5 +73,39 @@ int align_launch_tiled(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t 
                        int64_t max_pos, size_t lds, const KParams &kp, int32_t *d_scores, int32_t *d_final7,
                        uint32_t *d_tb, const int64_t *d_tb_off, void *d_faces, const int64_t *d_face_off,
                        hipStream_t stream);
+
+// The strip kernel (align_strip_kernel.hip): a strip is one tile row of the
+// tiled kernel, TY rows of y with all of z and x. A forward launch keeps the y
+// face of every strip but the last; strip launch j then sweeps strip
+// nty-1-j of every triple again, with pointers, into a cube of one strip, and
+// tb_walk_strip follows them before launch j+1 overwrites it.
+// Bytes of a triple's strip cube, TY*(la+lc-1)*lc words.
+size_t align_strip_cube_bytes(int32_t la, int32_t lb, int32_t lc, int32_t tymax, int32_t tzmax);
+// 16-byte cells of its face workspace: nty-1 kept y faces [la][lc+1] and two
+// z faces [la][TY].
+size_t align_strip_face_cells(int32_t la, int32_t lb, int32_t lc, int32_t tymax, int32_t tzmax);
+// The walker record of a triple, int32 words {x, y, z, T, n, done}: where the
+// walk stands, the state it is in, the moves it has made and whether the path
+// has reached a zero face.
+constexpr int ALIGN_WALK_REC = 6;
+// One launch for n triples through launch_with_lds: j < 0 the forward form
+// (strips 0 .. nty-2, no pointers), j >= 0 strip launch j, which skips a triple
+// with fewer than j+1 strips or whose record in d_walk is done. max_pos, lds
+// and d_face_off as align_launch_tiled's, over align_strip_face_cells;
+// d_tb_off[t] = the word offset of triple t's strip cube.
+int align_launch_strip(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, int32_t tymax, int32_t tzmax,
+                       int64_t max_pos, size_t lds, const KParams &kp, int32_t j, const int32_t *d_walk,
+                       int32_t *d_scores, int32_t *d_final7, uint32_t *d_tb, const int64_t *d_tb_off, void *d_faces,
+                       const int64_t *d_face_off, hipStream_t stream);
+// The walk after strip launch j, one walker (thread) per triple: it follows
+// the pointers of strip s = nty-1-j from where its record in walk stands (from
+// (la,lb,lc) and final7 when j = 0) while the cell lies in the strip, y > s*TY,
+// appending to moves[offs[3t] ..) from the end backwards. A predecessor on a
+// zero face ends the path: done is set, {moves, x0, y0, z0} go to info[4t] and
+// the walker reverses its slice into forward order. A predecessor in the strip
+// below saves the record for launch j+1.
+__global__ void tb_walk_strip(const uint32_t *tb, const int64_t *tb_off, const int64_t *offs, int32_t n,
+                              int32_t tymax, int32_t tzmax, int32_t j, const int32_t *final7, int32_t *walk,
+                              uint8_t *moves, int32_t *info);
 
 }  // namespace tsa

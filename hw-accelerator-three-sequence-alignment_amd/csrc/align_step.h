@@ -1,8 +1,9 @@
-// align_step.h -- what the two resident traceback kernels share: the staging
+// align_step.h -- what the resident traceback kernels share: the staging
 // and the lookup of A's symbols, the register state of a (y,z) position and
 // one step of the schedule for it. align_kernel.hip explains the schedule and
 // calls the step with its whole plane as the one tile; align_tiled_kernel.hip
-// calls it tile by tile. The cell is literal_cell.h's max7_literal on the
+// and align_strip_kernel.hip call it tile by tile, the forward form of the
+// latter without the pointer word. The cell is literal_cell.h's max7_literal on the
 // plane sweep's operands (src/PE_1cyc.v:159-218, MAX7 src/PE_1cyc.v:1-32).
 //
 // Both kernels sit at the SGPR limit, where one more SGPR is a spilled VGPR, and
@@ -65,7 +66,9 @@ struct AlignPos {
   // 0 <= x = q-y-z <= la reads rd = buf[(q-1)&1] (row stride ldz) and, while
   // x >= 1, publishes its cell into wr = buf[q&1], stores its pointer word in
   // cube and, at the cube's end (la,lb,lc), the triple's score and final states.
-  template <class SymA>
+  // TB = false (the forward form of align_strip_kernel.hip): the cells alone,
+  // no argmax, no pointer word, no score.
+  template <bool TB = true, class SymA>
   __device__ __forceinline__ void step(const uint4 *rd, uint4 *wr, int32_t ldz, int32_t q, int32_t la, int32_t y0,
                                        int32_t z0, int32_t lb, int32_t lc, uint32_t *cube, const KParams &kp,
                                        int64_t t, int32_t *scores, int32_t *final7, const SymA &symA) {
@@ -80,7 +83,7 @@ struct AlignPos {
       if (x == 0) {  // M of x = 1 comes from the corner of the zero faces
         const int32_t zero7[7] = {0, 0, 0, 0, 0, 0, 0};
         literal_adds(kp, symA(0), b, cc, sh, sab, sbc, sac, s3);
-        hM3 = max7_literal<SM, true>(zero7, kp, s3, sh, g);
+        hM3 = max7_literal<SM, TB>(zero7, kp, s3, sh, g);
         gh = (gh & ~(7u << 9)) | (g << 9);
       } else {
         int32_t S[7];
@@ -91,23 +94,25 @@ struct AlignPos {
         S[SIYZ] = hYZ;
         S[SIXZ] = hXZ;
         unpack7(rd[idx], pr);  // own: (x-1, y, z)
-        S[SIX] = max7_literal<SIX, true>(pr, kp, 0, sh, g);
+        S[SIX] = max7_literal<SIX, TB>(pr, kp, 0, sh, g);
         w |= g << (3 * SIX);
         unpack7(rd[idx - ldz], pr);  // N1: (x, y-1, z)
-        S[SIY] = max7_literal<SIY, true>(pr, kp, 0, sh, g);
+        S[SIY] = max7_literal<SIY, TB>(pr, kp, 0, sh, g);
         w |= g << (3 * SIY);
         unpack7(rd[idx - 1], pr);  // W1: (x, y, z-1)
-        S[SIZ] = max7_literal<SIZ, true>(pr, kp, 0, sh, g);
+        S[SIZ] = max7_literal<SIZ, TB>(pr, kp, 0, sh, g);
         w |= g << (3 * SIZ);
         wr[idx] = pack7(S);
-        cube[tb_index(x, y0 + y, z0 + z, la, lc)] = w;
-        if (x == la && y0 + y == lb && z0 + z == lc) {  // FINAL_MAX, src/TriAlign_1cyc.v:141-142
-          int32_t m = S[0];
+        if constexpr (TB) {
+          cube[tb_index(x, y0 + y, z0 + z, la, lc)] = w;
+          if (x == la && y0 + y == lb && z0 + z == lc) {  // FINAL_MAX, src/TriAlign_1cyc.v:141-142
+            int32_t m = S[0];
 #pragma unroll
-          for (int s = 1; s < NSTATE; ++s) m = max(m, S[s]);
-          scores[t] = m;
+            for (int s = 1; s < NSTATE; ++s) m = max(m, S[s]);
+            scores[t] = m;
 #pragma unroll
-          for (int s = 0; s < NSTATE; ++s) final7[t * NSTATE + s] = S[s];
+            for (int s = 0; s < NSTATE; ++s) final7[t * NSTATE + s] = S[s];
+          }
         }
         hM3 = hM2;
         gh = (gh & ~(7u << 9)) | (((gh >> 12) & 7u) << 9);
@@ -116,16 +121,16 @@ struct AlignPos {
       uint32_t gn = gh & (7u << 9);
       literal_adds(kp, symA(x), b, cc, sh, sab, sbc, sac, s3);  // a_{x+1}
       unpack7(rd[idx - ldz], pr);  // N1 = (x, y-1, z): Ixy of x+1
-      hXY = max7_literal<SIXY, true>(pr, kp, sab, sh, g);
+      hXY = max7_literal<SIXY, TB>(pr, kp, sab, sh, g);
       gn |= g;
       unpack7(rd[idx - 1], pr);  // W1 = (x, y, z-1): Ixz of x+1
-      hXZ = max7_literal<SIXZ, true>(pr, kp, sac, sh, g);
+      hXZ = max7_literal<SIXZ, TB>(pr, kp, sac, sh, g);
       gn |= g << 6;
       unpack7(rd[idx - ldz - 1], pr);  // NW1 = (x+1, y-1, z-1): Iyz of x+1, M of x+2
-      hYZ = max7_literal<SIYZ, true>(pr, kp, sbc, sh, g);
+      hYZ = max7_literal<SIYZ, TB>(pr, kp, sbc, sh, g);
       gn |= g << 3;
       literal_adds(kp, symA(x + 1), b, cc, sh, sab, sbc, sac, s3);  // a_{x+2}
-      hM2 = max7_literal<SM, true>(pr, kp, s3, sh, g);
+      hM2 = max7_literal<SM, TB>(pr, kp, s3, sh, g);
       gh = gn | (g << 12);
     }
   }

@@ -266,11 +266,36 @@ int tsa_align_batch(const uint8_t *seqs, const int64_t *offsets, int32_t n,
                     const tsa_params *p, int32_t *scores, uint8_t *moves,
                     int32_t *n_moves, int32_t *starts, int32_t device);
 
+/* tsa_align_batch for cubes whose pointer cube exceeds the budget: the same
+ * signature, validation, error codes, thread safety and results, move for
+ * move, with the plan mode strip unless the override align_mode is set (a set
+ * override holds, as everywhere). Triples that fit one workgroup stay with the
+ * resident kernel and a whole cube. Every other triple takes the strip path: a
+ * strip is one tile row of the tiled kernel, TY rows of y with all of z and x
+ * (the same tiles, caps and align_tile override; nty strips). A forward launch
+ * sweeps strips 0 .. nty-2 without pointers and keeps the last row of each,
+ * which is all the strip above depends on; then launch j = 0, 1, .. sweeps
+ * strip nty-1-j of every triple again with pointers into a cube of one strip,
+ * and a walk launch follows them until the path leaves the strip or ends --
+ * the strips above a path's end are not swept. Per strip triple the need is
+ *   4*TY*(la+lc-1)*lc + 16*((nty-1)*la*(lc+1) + 2*la*TY)  bytes
+ * (strip cube + kept faces, both counted against the budget; the full cube
+ * for a resident triple), about 1/nty of the cube for at most twice the cell
+ * work. A chunk holds consecutive triples whose needs fit the budget, and
+ * TSA_ENOMEM is returned only when one triple's own need exceeds it. A chunk
+ * queues [resident] + [forward, if a strip triple has nty >= 2] + max nty
+ * counted launches (tsa_kernel_launch_count). */
+int tsa_align_batch_lowmem(const uint8_t *seqs, const int64_t *offsets, int32_t n,
+                           const tsa_params *p, int32_t *scores, uint8_t *moves,
+                           int32_t *n_moves, int32_t *starts, int32_t device);
+
 /* Which path tsa_align_batch takes for a group (one chunk) of n triples of
  * these lengths under the current overrides, as a short text that begins with
- * "resident", "tiled" or "plane"; for tiled it carries the tile and the tile
- * grid, such as "tiled tile=64x43 tiles=4x6 lds=91632 faces=5259264" (lds:
- * dynamic LDS of the workgroup, faces: bytes of the triple's face workspace).
+ * "resident", "tiled", "strip" or "plane"; for tiled it carries the tile and
+ * the tile grid, such as "tiled tile=64x43 tiles=4x6 lds=91632 faces=5259264"
+ * (lds: dynamic LDS of the workgroup, faces: bytes of the triple's face
+ * workspace), for strip also the bytes of the strip cube, such as
+ * "strip tile=7x7 tiles=3x3 lds=2080 cube=16240 faces=8960".
  * It is built from the functions the dispatch uses. Host-only, no device
  * needed. TSA_EINVAL for a null or empty buffer, n or a length below 1, bad
  * parameters, or an align_mode / align_tile value that is not valid. */
@@ -299,7 +324,8 @@ int64_t tsa_check_fallback_count(void);
 
 /* Kernel launches with dynamic LDS (helix, lap, literal helix; the resident
  * and the tiled resident traceback kernel of tsa_align_batch, each one per
- * chunk that has triples for it) the library has queued
+ * chunk that has triples for it; the forward and the strip launches of the
+ * strip path) the library has queued
  * since it was loaded: a call that reuses an error left over from an earlier
  * HIP call must still launch its kernel exactly once (tests). The plane sweep
  * and the traceback walks are not counted. */
@@ -333,14 +359,15 @@ const char *tsa_version(void);
  *   lap_spin_limit  polls before a lap hand-off times out (0: at once)
  *   lap_trace       path of a per-workgroup timestamp CSV (tools/lap_trace.py)
  *   split_serial    0 | 1           (tsa_score_gpu_multi parts one by one)
- *   align_mode      resident | plane | tiled (tsa_align_batch: resident still
- *                   sends a triple that does not fit a workgroup to the plane
- *                   sweep; tiled sends it to the tiled resident kernel, and no
- *                   triple to the plane sweep)
+ *   align_mode      resident | plane | tiled | strip (tsa_align_batch: resident
+ *                   still sends a triple that does not fit a workgroup to the
+ *                   plane sweep; tiled sends it to the tiled resident kernel,
+ *                   strip to the strip path of tsa_align_batch_lowmem, and
+ *                   under either no triple takes the plane sweep)
  *   align_tb_bytes  pointer-cube budget of a tsa_align_batch chunk, in bytes
  *   align_tile      TYxTZ, e.g. 5x7: caps the tile edges of the tiled kernel;
- *                   under align_mode = tiled every triple larger than the tile
- *                   is tiled, even one that would fit a workgroup. A malformed
+ *                   under align_mode = tiled or strip every triple larger than
+ *                   the tile is tiled, even one that would fit a workgroup. A malformed
  *                   value, an edge below 1 or a tile over the tiled kernel's
  *                   capacity (the resident capacity, and TY*TZ <= 3072) makes tsa_align_batch and tsa_describe_align_plan return
  *                   TSA_EINVAL

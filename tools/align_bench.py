@@ -7,7 +7,12 @@ synchronous, so host wall time is the time a caller waits.
   python tools/align_bench.py --n 512 --la 64 --lb 64 --lc 64
   python tools/align_bench.py --n 64 --la 64 --related
   python tools/align_bench.py --n 256 --la 256 --forms tiled,plane
-(a form other than loop is passed to align_mode as it stands).
+  python tools/align_bench.py --n 256 --la 256 --forms tiled,strip
+  python tools/align_bench.py --n 8 --la 512 --forms tiled,strip --tb-bytes 1073741824
+(a form other than loop is passed to align_mode as it stands: resident, plane,
+tiled or strip; --tb-bytes sets align_tb_bytes for every batch form, and a form
+the library refuses, such as tiled with a cube over that budget, is recorded
+with its error instead of a time).
 A library without tsa_align_batch (an older build named by TSA_PKG_DIR) runs
 the loop alone: that is how the baseline of a comparison is taken.
 Prints one JSON line: per form the median, min and max of the passes in ms."""
@@ -32,7 +37,9 @@ def main():
     ap.add_argument("--passes", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--loop-n", type=int, default=None, help="triples of the align loop (default: all)")
-    ap.add_argument("--forms", default="resident,plane,loop")
+    ap.add_argument("--forms", default="resident,plane,loop",
+                    help="comma list of loop and align_mode values: resident, plane, tiled, strip")
+    ap.add_argument("--tb-bytes", type=int, default=None, help="align_tb_bytes of the batch forms")
     args = ap.parse_args()
     import bench
     tsa = bench.load_pkg()
@@ -51,7 +58,10 @@ def main():
 
     def batch(mode):
         def run():
-            with tsa.overrides(align_mode=mode):
+            ov = dict(align_mode=mode)
+            if args.tb_bytes is not None:
+                ov["align_tb_bytes"] = args.tb_bytes
+            with tsa.overrides(**ov):
                 return tsa.align_batch(seqs=seqs, offsets=offs)
         return run
 
@@ -64,7 +74,13 @@ def main():
             forms[f] = loop
         elif have_batch:
             forms[f] = batch(f)
-    out = {f: fn() for f, fn in forms.items()}       # first call: also the cross-check
+    out, refused = {}, {}
+    for f, fn in list(forms.items()):                # first call: also the cross-check
+        try:
+            out[f] = fn()
+        except tsa.TsaError as e:                    # e.g. TSA_ENOMEM: the form cannot run this batch
+            refused[f] = str(e)
+            del forms[f]
     names = list(out)
     same = True
     for f in names[1:]:
@@ -81,6 +97,10 @@ def main():
     res = {"bench": "align", "n": args.n, "shape": [la, lb, lc], "related": bool(args.related),
            "passes": args.passes, "warmup": args.warmup, "loop_n": loop_n, "forms_agree": same,
            "version": tsa.version()}
+    if args.tb_bytes is not None:
+        res["tb_bytes"] = args.tb_bytes
+    for f, why in refused.items():
+        res[f + "_error"] = why
     for f, ts in times.items():
         scale = args.n / loop_n if f == "loop" else 1.0  # a shortened loop, scaled to the batch
         res[f + "_ms"] = {"median": round(statistics.median(ts) * scale, 3), "min": round(min(ts) * scale, 3),
