@@ -12,6 +12,7 @@ from __future__ import annotations
 import ctypes
 import os
 import subprocess
+from typing import NamedTuple
 
 import numpy as np
 
@@ -55,6 +56,15 @@ def lib() -> ctypes.CDLL:
         L.tsao_score_msg.restype = ctypes.c_int
         L.tsao_state_range.argtypes = three + [pp, i32p, i32p]
         L.tsao_state_range.restype = ctypes.c_int
+        L.tsao_best_range.argtypes = three + [pp, ctypes.c_int32, ctypes.c_int32, i32p, i32p,
+                                              i32p, i32p, i64p, i64p]
+        L.tsao_best_range.restype = ctypes.c_int
+        L.tsao_penalty_table.argtypes = [pp, i32p]
+        L.tsao_penalty_table.restype = None
+        L.tsao_s2.argtypes = [ctypes.c_int, ctypes.c_int, pp]
+        L.tsao_s2.restype = ctypes.c_int32
+        L.tsao_s3.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, pp]
+        L.tsao_s3.restype = ctypes.c_int32
         L.tsao_score_batch.argtypes = [u8p, i64p, ctypes.c_int32, pp, i32p, ctypes.c_int32]
         L.tsao_score_batch.restype = ctypes.c_int
         L.tsao_rtl_run.argtypes = three + [ctypes.c_int32, i32p, i32p,
@@ -128,6 +138,57 @@ def state_range(a, b, c, params: OracleParams | None = None) -> tuple[int, int]:
     if rc:
         raise ValueError(f"oracle rc={rc}")
     return int(lo.value), int(hi.value)
+
+
+class BestRange(NamedTuple):
+    """tsao_best_range: the unwrapped literal recurrence's per-cell MAX7 over
+    the real cells (x, y, z >= 1)."""
+    bmin: int
+    bmax: int
+    at_min: tuple  # first cell (x, y, z order) attaining bmin
+    at_max: tuple  # first cell attaining bmax
+    n_above: int   # cells with best > hi_thr
+    n_below: int   # cells with best < lo_thr
+
+
+def best_range(a, b, c, params: OracleParams | None = None, hi_thr: int = 2**31 - 1,
+               lo_thr: int = -2**31) -> BestRange:
+    """Range of `best` the checked kernel's monitor watches:
+    the x-plane literal sweep with score_bits forced to 0 (src/PE_1cyc.v:1-32,
+    164-218 without the wordsize wrap of :127-133)."""
+    p = params or default_params()
+    A, B, C = _u8(a), _u8(b), _u8(c)
+    lo, hi = ctypes.c_int32(0), ctypes.c_int32(0)
+    amin, amax = (ctypes.c_int32 * 3)(), (ctypes.c_int32 * 3)()
+    na, nb = ctypes.c_int64(0), ctypes.c_int64(0)
+    rc = lib().tsao_best_range(_p(A, ctypes.c_uint8), len(A), _p(B, ctypes.c_uint8), len(B),
+                               _p(C, ctypes.c_uint8), len(C), ctypes.byref(p), hi_thr, lo_thr,
+                               ctypes.byref(lo), ctypes.byref(hi), amin, amax,
+                               ctypes.byref(na), ctypes.byref(nb))
+    if rc:
+        raise ValueError(f"oracle rc={rc}")
+    return BestRange(int(lo.value), int(hi.value), tuple(int(v) for v in amin),
+                     tuple(int(v) for v in amax), int(na.value), int(nb.value))
+
+
+def penalty_table(params: OracleParams | None = None) -> np.ndarray:
+    """P[target][source] of tsao_penalty_table (src/PE_1cyc.v:164-218)."""
+    p = params or default_params()
+    out = np.zeros((7, 7), dtype=np.int32)
+    lib().tsao_penalty_table(ctypes.byref(p), _p(out, ctypes.c_int32))
+    return out
+
+
+def s2(u: int, v: int, params: OracleParams | None = None) -> int:
+    """Pair score of the PE (src/PE_1cyc.v:159-161)."""
+    p = params or default_params()
+    return int(lib().tsao_s2(u, v, ctypes.byref(p)))
+
+
+def s3(u: int, v: int, w: int, params: OracleParams | None = None) -> int:
+    """Triple score of the PE (src/PE_1cyc.v:162, or sum-of-pairs by s3_mode)."""
+    p = params or default_params()
+    return int(lib().tsao_s3(u, v, w, ctypes.byref(p)))
 
 
 def rtl_run(a, b, c, a_total_len: int = 512) -> tuple[int, bool, int]:

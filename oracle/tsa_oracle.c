@@ -181,6 +181,73 @@ int tsao_score_xplane(const uint8_t *a, int32_t la, const uint8_t *b, int32_t lb
   return TSA_OK;
 }
 
+/* ---- best-range probe -------------------------------------------------------
+ * The x-plane literal sweep above with score_bits forced to 0 (no candidate
+ * wraps, src/PE_1cyc.v:127-133 widened without bound), folding every real
+ * cell's MAX7 (src/PE_1cyc.v:1-32 applied to the cell's 7 states, as
+ * FINAL_MAX does at (LA,LB,LC), src/TriAlign_1cyc.v:141-142) into a range.
+ * Cells are visited in (x, y, z) order and the comparisons are strict, so
+ * at_min / at_max name the first cell attaining each extreme. */
+int tsao_best_range(const uint8_t *a, int32_t la, const uint8_t *b, int32_t lb,
+                    const uint8_t *c, int32_t lc, const tsa_params *p, int32_t hi_thr,
+                    int32_t lo_thr, int32_t *bmin, int32_t *bmax, int32_t *at_min,
+                    int32_t *at_max, int64_t *n_above, int64_t *n_below) {
+  int rc = check_args(a, la, b, lb, c, lc, p);
+  if (rc) return rc;
+  if (!bmin || !bmax) return TSA_EINVAL;
+  tsa_params pw = *p;
+  pw.score_bits = 0;
+  int32_t P[7][7];
+  tsao_penalty_table(&pw, P);
+  const size_t W = (size_t)lc + 1, H = (size_t)lb + 1;
+  const size_t plane = W * H * 7;
+  int32_t *prev = (int32_t *)calloc(plane, sizeof(int32_t)); /* x-1; x=0 face = 0 */
+  int32_t *cur = (int32_t *)calloc(plane, sizeof(int32_t));  /* y=0/z=0 faces stay 0 */
+  if (!prev || !cur) { free(prev); free(cur); return TSA_ENOMEM; }
+  int32_t s3_tab[4][4][4], s2_tab[4][4]; /* src/PE_1cyc.v:159-162 */
+  for (int u = 0; u < 4; ++u)
+    for (int v = 0; v < 4; ++v) {
+      s2_tab[u][v] = tsao_s2(u, v, &pw);
+      for (int w = 0; w < 4; ++w) s3_tab[u][v][w] = tsao_s3(u, v, w, &pw);
+    }
+  int32_t lo = 0, hi = 0, amin[3] = {0, 0, 0}, amax[3] = {0, 0, 0};
+  int64_t above = 0, below = 0;
+  for (int32_t x = 1; x <= la; ++x) {
+    const int ax = a[x - 1] & 3;
+    for (int32_t y = 1; y <= lb; ++y) {
+      const int by = b[y - 1] & 3;
+      const int32_t *prow = prev + (size_t)y * W * 7, *prow1 = prev + (size_t)(y - 1) * W * 7;
+      int32_t *crow = cur + (size_t)y * W * 7;
+      const int32_t *crow1 = cur + (size_t)(y - 1) * W * 7;
+      for (int32_t z = 1; z <= lc; ++z) {
+        const int cz = c[z - 1] & 3;
+        cell_literal(prow1 + (z - 1) * 7, prow + z * 7, crow1 + z * 7, crow + (z - 1) * 7,
+                     prow1 + z * 7, crow1 + (z - 1) * 7, prow + (z - 1) * 7,
+                     s3_tab[ax][by][cz], s2_tab[ax][by], s2_tab[by][cz], s2_tab[ax][cz], P, 0,
+                     crow + z * 7);
+        const int32_t best = best7(crow + z * 7);
+        const int first = x == 1 && y == 1 && z == 1;
+        if (first || best < lo) { lo = best; amin[0] = x; amin[1] = y; amin[2] = z; }
+        if (first || best > hi) { hi = best; amax[0] = x; amax[1] = y; amax[2] = z; }
+        above += best > hi_thr;
+        below += best < lo_thr;
+      }
+    }
+    int32_t *t = prev;
+    prev = cur;
+    cur = t;
+  }
+  *bmin = lo;
+  *bmax = hi;
+  if (at_min) memcpy(at_min, amin, sizeof(amin));
+  if (at_max) memcpy(at_max, amax, sizeof(amax));
+  if (n_above) *n_above = above;
+  if (n_below) *n_below = below;
+  free(prev);
+  free(cur);
+  return TSA_OK;
+}
+
 int tsao_score_diag(const uint8_t *a, int32_t la, const uint8_t *b, int32_t lb,
                     const uint8_t *c, int32_t lc, const tsa_params *p,
                     int32_t *score, int32_t *final7) {

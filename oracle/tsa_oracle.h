@@ -75,6 +75,17 @@ int tsao_state_range(const uint8_t *a, int32_t la, const uint8_t *b, int32_t lb,
                      const uint8_t *c, int32_t lc, const tsa_params *p,
                      int32_t *lo, int32_t *hi);
 
+/* Min / max over the real cells (x, y, z >= 1) of the per-cell MAX7 ("best")
+ * of the literal recurrence run unwrapped (score_bits forced to 0) -- the
+ * quantity the checked kernel's range monitor certifies.
+ * at_min / at_max (nullable, 3 ints each): the first cell in (x, y, z) order
+ * attaining each; n_above / n_below (nullable): cells with best > hi_thr /
+ * best < lo_thr. MAX7: src/PE_1cyc.v:1-32; candidates: src/PE_1cyc.v:164-218. */
+int tsao_best_range(const uint8_t *a, int32_t la, const uint8_t *b, int32_t lb,
+                    const uint8_t *c, int32_t lc, const tsa_params *p, int32_t hi_thr,
+                    int32_t lo_thr, int32_t *bmin, int32_t *bmax, int32_t *at_min,
+                    int32_t *at_max, int64_t *n_above, int64_t *n_below);
+
 /* n triples laid out as in tsa_score_batch(); nthreads POSIX threads, one
  * triple at a time per thread (tsao_score_xplane). */
 int tsao_score_batch(const uint8_t *seqs, const int64_t *offsets, int32_t n,
