@@ -65,6 +65,7 @@ EXPORTS = (
     "tsa_fallback_count", "tsa_check_fallback_count", "tsa_score_batch_async_p2", "tsa_pack2",
     "tsa_score_gpu_multi", "tsa_score_batch_devices", "tsa_set_override", "tsa_get_overrides",
     "tsa_kernel_launch_count", "tsa_align_batch", "tsa_describe_align_plan", "tsa_align_batch_lowmem",
+    "tsa_align_batch_grid",
 )
 
 # Plan overrides the library accepts (tsa_set_override; include/trialign.h).
@@ -148,6 +149,7 @@ def _load_lib() -> ctypes.CDLL:
     lib.tsa_align_batch.argtypes = [u8p, i64p, ctypes.c_int32, pp, i32p, u8p, i32p, i32p,
                                     ctypes.c_int32]
     lib.tsa_align_batch_lowmem.argtypes = lib.tsa_align_batch.argtypes
+    lib.tsa_align_batch_grid.argtypes = lib.tsa_align_batch.argtypes
     lib.tsa_score_gpu_multi.argtypes = [u8p, ctypes.c_int32, u8p, ctypes.c_int32, u8p,
                                         ctypes.c_int32, pp, i32p, ctypes.c_int32, i32p,
                                         ctypes.POINTER(ctypes.c_double)]
@@ -171,7 +173,7 @@ def _load_lib() -> ctypes.CDLL:
                  "tsa_describe_plan", "tsa_align_gpu", "tsa_score_batch_async_p2", "tsa_pack2",
                  "tsa_score_gpu_multi", "tsa_score_batch_devices", "tsa_set_override",
                  "tsa_get_overrides", "tsa_align_batch", "tsa_describe_align_plan",
-                 "tsa_align_batch_lowmem"):
+                 "tsa_align_batch_lowmem", "tsa_align_batch_grid"):
         getattr(lib, name).restype = ctypes.c_int
     return lib
 
@@ -370,7 +372,7 @@ def align(a, b, c, params: Optional[TsaParams] = None, device: int = 0):
 
 def align_batch(triples=None, params: Optional[TsaParams] = None, device: int = 0,
                 seqs: Optional[np.ndarray] = None, offsets: Optional[np.ndarray] = None,
-                lowmem: bool = False) -> list:
+                lowmem: bool = False, grid: bool = False) -> list:
     """Optimal alignments of many triples in one call (tsa_align_batch): a
     list of ``(score, start, moves)``, one per triple in the caller's order,
     each as ``align`` returns it. Triples whose (y,z) planes fit a workgroup
@@ -381,7 +383,15 @@ def align_batch(triples=None, params: Optional[TsaParams] = None, device: int = 
     ``lowmem=True`` calls tsa_align_batch_lowmem: the same results, the larger
     triples by the strip path (``align_mode="strip"`` unless that override is
     set), which keeps the pointers of one tile row of a cube at a time, so
-    cubes over the budget can be aligned, for up to twice the cell work."""
+    cubes over the budget can be aligned, for up to twice the cell work.
+    ``grid=True`` calls tsa_align_batch_grid: the same results, the larger
+    triples by the grid path (``align_mode="grid"`` unless that override is
+    set), which keeps the last row and column of every tile, sweeps the tiles
+    of a diagonal of the tile grid in parallel and sweeps again, with the
+    pointers of one tile, only the tiles on the path. ``lowmem`` and ``grid``
+    together raise ``TsaError(TSA_EINVAL)``."""
+    if lowmem and grid:
+        raise TsaError(TSA_EINVAL, "align_batch(lowmem=True, grid=True)")
     p = params or TsaParams.default()
     if seqs is None:
         seqs, offsets = pack_batch(triples)
@@ -392,7 +402,7 @@ def align_batch(triples=None, params: Optional[TsaParams] = None, device: int = 
     nm = np.zeros(max(n, 1), dtype=np.int32)
     st = np.zeros(max(3 * n, 1), dtype=np.int32)
     mv = np.zeros(max(int(offsets[-1] - offsets[0]) if n else 0, 1), dtype=np.uint8)
-    name = "tsa_align_batch_lowmem" if lowmem else "tsa_align_batch"
+    name = "tsa_align_batch_lowmem" if lowmem else "tsa_align_batch_grid" if grid else "tsa_align_batch"
     rc = getattr(_lib, name)(_ptr(seqs, ctypes.c_uint8), _ptr(offsets, ctypes.c_int64), n,
                              ctypes.byref(p), _ptr(sc, ctypes.c_int32), _ptr(mv, ctypes.c_uint8),
                              _ptr(nm, ctypes.c_int32), _ptr(st, ctypes.c_int32), device)
@@ -547,7 +557,9 @@ def describe_align_plan(n: int, la: int, lb: int, lc: int, params: Optional[TsaP
     ``align_batch`` under the current overrides (tsa_describe_align_plan;
     host-only): ``resident ...``, ``tiled tile=TYxTZ tiles=NYxNZ ...``,
     ``strip tile=TYxTZ tiles=NYxNZ lds=... cube=<strip cube bytes> faces=<face
-    bytes>`` (``align_mode="strip"``, what ``align_batch(lowmem=True)`` plans)
+    bytes>`` (``align_mode="strip"``, what ``align_batch(lowmem=True)`` plans),
+    ``grid tile=TYxTZ tiles=NYxNZ lds=... cube=<tile cube bytes> faces=<kept
+    face bytes>`` (``align_mode="grid"``, what ``align_batch(grid=True)`` plans)
     or ``plane``."""
     p = params or TsaParams.default()
     buf = ctypes.create_string_buffer(256)

@@ -1,10 +1,11 @@
 // align_api.hip -- the traceback entry points of include/trialign.h:
-// tsa_align_batch, tsa_align_batch_lowmem, tsa_align_gpu (one triple, always
-// the plane sweep) and tsa_describe_align_plan. Host code only: which path a
-// triple takes, the chunks of pointer cubes, the device buffers and the
+// tsa_align_batch, tsa_align_batch_lowmem, tsa_align_batch_grid, tsa_align_gpu
+// (one triple, always the plane sweep) and tsa_describe_align_plan. Host code
+// only: which path a triple takes, the chunks of pointer cubes, the device buffers and the
 // launches of the resident kernel (align_kernel.hip), the tiled resident kernel
-// (align_tiled_kernel.hip), the strip kernel (align_strip_kernel.hip), the
-// batched plane sweep and the batched walks (plane_kernel.hip).
+// (align_tiled_kernel.hip), the strip kernel (align_strip_kernel.hip), the grid
+// kernels (align_grid_kernel.hip), the batched plane sweep and the batched
+// walks (plane_kernel.hip).
 //
 // Traceback is an extension: the reference's alignment-output ports are
 // commented out (src/TriAlign_tb.sv:239-260).
@@ -50,9 +51,15 @@ struct AlignBufs {
 // and take the plane sweep otherwise. Under align_mode = strip (what
 // tsa_align_batch_lowmem plans by default) they take the strip path instead,
 // which keeps the pointers of one tile row of a cube at a time: never chosen
-// without being asked for, since it sweeps most cells twice.
-enum AlignPath { ALIGN_RESIDENT, ALIGN_TILED, ALIGN_PLANE, ALIGN_STRIP };
-enum AlignMode { ALIGN_MODE_AUTO, ALIGN_MODE_RESIDENT, ALIGN_MODE_PLANE, ALIGN_MODE_TILED, ALIGN_MODE_STRIP };
+// without being asked for, since it sweeps most cells twice. Under align_mode =
+// grid (what tsa_align_batch_grid plans by default) they take the grid path,
+// which keeps the faces of every tile, sweeps the tiles of a diagonal of the
+// tile grid as workgroups of their own and sweeps again, with the pointers of
+// one tile, only the tiles on the path: opt-in as well.
+enum AlignPath { ALIGN_RESIDENT, ALIGN_TILED, ALIGN_PLANE, ALIGN_STRIP, ALIGN_GRID };
+enum AlignMode {
+  ALIGN_MODE_AUTO, ALIGN_MODE_RESIDENT, ALIGN_MODE_PLANE, ALIGN_MODE_TILED, ALIGN_MODE_STRIP, ALIGN_MODE_GRID
+};
 struct AlignPlan {
   AlignMode mode = ALIGN_MODE_AUTO;
   bool mode_set = false;  // align_mode is set
@@ -74,6 +81,7 @@ int align_plan_read(AlignPlan *pl) {
     else if (!strcmp(v, "plane")) pl->mode = ALIGN_MODE_PLANE;
     else if (!strcmp(v, "tiled")) pl->mode = ALIGN_MODE_TILED;
     else if (!strcmp(v, "strip")) pl->mode = ALIGN_MODE_STRIP;
+    else if (!strcmp(v, "grid")) pl->mode = ALIGN_MODE_GRID;
     else return TSA_EINVAL;
     pl->mode_set = true;
   }
@@ -95,10 +103,10 @@ int align_plan_read(AlignPlan *pl) {
 }
 
 // Over capacity: the triple does not go to the resident kernel as a whole.
-// With align_tile set under align_mode = tiled or strip that is any triple
+// With align_tile set under align_mode = tiled, strip or grid that is any triple
 // larger than the tile (tests put tiny cubes through many tiles that way).
 bool align_over(const AlignPlan &pl, int32_t la, int32_t lb, int32_t lc) {
-  if ((pl.mode == ALIGN_MODE_TILED || pl.mode == ALIGN_MODE_STRIP) && pl.capped)
+  if ((pl.mode == ALIGN_MODE_TILED || pl.mode == ALIGN_MODE_STRIP || pl.mode == ALIGN_MODE_GRID) && pl.capped)
     return lb > pl.tymax || lc > pl.tzmax;
   return !align_resident_fits(la, lb, lc);
 }
@@ -107,6 +115,7 @@ bool align_over(const AlignPlan &pl, int32_t la, int32_t lb, int32_t lc) {
 AlignPath align_over_path(const AlignPlan &pl, int32_t n_over) {
   if (pl.mode == ALIGN_MODE_TILED) return ALIGN_TILED;
   if (pl.mode == ALIGN_MODE_STRIP) return ALIGN_STRIP;
+  if (pl.mode == ALIGN_MODE_GRID) return ALIGN_GRID;
   if (pl.mode == ALIGN_MODE_AUTO && n_over >= kAlignTiledMinGroup) return ALIGN_TILED;
   return ALIGN_PLANE;
 }
@@ -121,11 +130,12 @@ AlignPath align_path(const AlignPlan &pl, int32_t la, int32_t lb, int32_t lc, in
 // buffers, the chunks and the launches all read these numbers.
 struct AlignTriple {
   int32_t la, lb, lc;
-  bool over;     // not the resident kernel's: tiled or plane, as its chunk decides, or strip
-  size_t cube;   // bytes of its pointer cube; of its strip cube on the strip path
-  size_t face;   // 16-byte cells of its face workspace if the chunk is tiled or strips
-  size_t need;   // what it takes of the budget: the cube; with the faces on the strip path, where they are O(N^3/TY)
+  bool over;     // not the resident kernel's: tiled or plane, as its chunk decides, or strip, or grid
+  size_t cube;   // bytes of its pointer cube; of its strip cube on the strip path, its tile cube on the grid path
+  size_t face;   // 16-byte cells of its face workspace if the chunk is tiled, strips or grid
+  size_t need;   // what it takes of the budget: the cube; with the faces on the strip and grid paths (O(N^3/TY))
   int32_t nty;   // its strips on the strip path
+  int32_t ntz;   // with nty its tile grid on the grid path
   int64_t pos;   // positions of its workgroup: lb*lc, or TY*TZ of an over-capacity triple's tiles
   size_t lds;    // align_resident_lds of that plane or tile
 };
@@ -133,8 +143,9 @@ struct AlignTriple {
 // of its own: what its launches and the buffers need.
 struct AlignChunk {
   int32_t i0, i1, n_over = 0;
-  bool tiled = false, strip = false;      // the path of the n_over over-capacity triples
+  bool tiled = false, strip = false, grid = false;  // the path of the n_over over-capacity triples
   int32_t max_nty = 0;                    // the strip launches: the most strips of a triple
+  int32_t max_diag = 0, max_len = 0;      // the grid launches: the most diagonals (nty+ntz-1), the longest diagonal
   size_t need = 0, cube = 0, seq = 0;     // bytes against the budget, of the cubes and of the sequences
   int64_t max_pos = 1, tile_pos = 1;      // the resident and the tiled launch
   size_t lds = 0, tile_lds = 0, face = 0; // face: bytes
@@ -152,14 +163,17 @@ int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KPar
     AlignTriple &t = T[i];
     t.la = (int32_t)(o[1] - o[0]), t.lb = (int32_t)(o[2] - o[1]), t.lc = (int32_t)(o[3] - o[2]);
     t.over = align_path(pl, t.la, t.lb, t.lc, 0) != ALIGN_RESIDENT;
-    const bool strip = t.over && pl.mode == ALIGN_MODE_STRIP;
-    t.cube = strip ? align_strip_cube_bytes(t.la, t.lb, t.lc, pl.tymax, pl.tzmax) : tb_cube_bytes(t.la, t.lb, t.lc);
+    const bool strip = t.over && pl.mode == ALIGN_MODE_STRIP, grid = t.over && pl.mode == ALIGN_MODE_GRID;
+    t.cube = strip  ? align_strip_cube_bytes(t.la, t.lb, t.lc, pl.tymax, pl.tzmax)
+             : grid ? align_grid_cube_bytes(t.la, t.lb, t.lc, pl.tymax, pl.tzmax)
+                    : tb_cube_bytes(t.la, t.lb, t.lc);
     const AlignTileGeom g = t.over ? align_tile_geom(t.lb, t.lc, pl.tymax, pl.tzmax) : AlignTileGeom{t.lb, t.lc, 1, 1};
     t.face = strip    ? align_strip_face_cells(t.la, t.lb, t.lc, pl.tymax, pl.tzmax)
+             : grid   ? align_grid_face_cells(t.la, t.lb, t.lc, pl.tymax, pl.tzmax)
              : t.over ? align_tiled_face_cells(t.la, t.lb, t.lc, pl.tymax, pl.tzmax)
                       : 0;
-    t.need = t.cube + (strip ? sizeof(uint4) * t.face : 0);
-    t.nty = g.nty;
+    t.need = t.cube + (strip || grid ? sizeof(uint4) * t.face : 0);
+    t.nty = g.nty, t.ntz = g.ntz;
     t.pos = (int64_t)g.TY * g.TZ;
     t.lds = align_resident_lds(t.la, g.TY, g.TZ);
   }
@@ -184,12 +198,15 @@ int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KPar
       c.tile_pos = std::max(c.tile_pos, t.pos), c.tile_lds = std::max(c.tile_lds, t.lds);
       c.face += sizeof(uint4) * t.face;
       c.max_nty = std::max(c.max_nty, t.nty);
+      c.max_diag = std::max(c.max_diag, t.nty + t.ntz - 1), c.max_len = std::max(c.max_len, std::min(t.nty, t.ntz));
       c.mla = std::max(c.mla, t.la), c.mlb = std::max(c.mlb, t.lb), c.mlc = std::max(c.mlc, t.lc);
     }
     c.i0 = i, c.i1 = j;
     c.tiled = c.n_over && align_over_path(pl, c.n_over) == ALIGN_TILED;
     c.strip = c.n_over && align_over_path(pl, c.n_over) == ALIGN_STRIP;
-    if (!c.tiled && !c.strip) c.face = 0, c.ws = c.n_over ? plane_workspace_bytes(c.n_over, c.mla, c.mlb, c.mlc) : 0;
+    c.grid = c.n_over && align_over_path(pl, c.n_over) == ALIGN_GRID;
+    if (!c.tiled && !c.strip && !c.grid)
+      c.face = 0, c.ws = c.n_over ? plane_workspace_bytes(c.n_over, c.mla, c.mlb, c.mlc) : 0;
     chunks.push_back(c);
     max_cube = std::max(max_cube, c.cube), max_seq = std::max(max_seq, c.seq);
     max_ws = std::max(max_ws, c.ws), max_face = std::max(max_face, c.face);
@@ -203,20 +220,22 @@ int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KPar
   int32_t *d_res = nullptr;   // m scores, 7m final states, 4m walk infos
   uint32_t *d_tb = nullptr;
   void *d_ws = nullptr, *d_faces = nullptr;
-  int32_t *d_walk = nullptr;  // the walker records of a chunk's strip triples
+  int32_t *d_walk = nullptr;  // the walker records of a chunk's strip or grid triples
   if (hipStreamCreateWithFlags(&B.s, hipStreamNonBlocking) != hipSuccess) return TSA_EDEVICE;
   if (!B.alloc(&d_seqs, max_seq) || !B.alloc(&d_moves, max_seq) ||
       !B.alloc(&d_meta, sizeof(int64_t) * (5 * (size_t)max_n + 1)) ||
       !B.alloc(&d_res, sizeof(int32_t) * 12 * (size_t)max_n) || !B.alloc(&d_tb, max_cube) ||
       !B.alloc(&d_ws, max_ws) || !B.alloc(&d_faces, max_face) ||
-      !B.alloc(&d_walk, pl.mode == ALIGN_MODE_STRIP ? sizeof(int32_t) * ALIGN_WALK_REC * (size_t)max_n : 0))
+      !B.alloc(&d_walk, pl.mode == ALIGN_MODE_STRIP || pl.mode == ALIGN_MODE_GRID
+                            ? sizeof(int32_t) * ALIGN_WALK_REC * (size_t)max_n
+                            : 0))
     return TSA_ENOMEM;
   std::vector<uint8_t> h_seqs(max_seq), h_moves(max_seq);
   std::vector<int64_t> h_meta(5 * (size_t)max_n + 1);
   std::vector<int32_t> h_res(12 * (size_t)max_n), order((size_t)max_n);
   for (const AlignChunk &c : chunks) {
-    // resident triples first, then the over-capacity ones (tiled, plane or strip,
-    // one path for all of a chunk), packed back to back, so each path sees a
+    // resident triples first, then the over-capacity ones (tiled, plane, strip or
+    // grid, one path for all of a chunk), packed back to back, so each path sees a
     // contiguous sub-batch
     const int32_t m = c.i1 - c.i0, mr = m - c.n_over;
     int32_t r = 0, v = mr;
@@ -231,7 +250,7 @@ int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KPar
       h_tboff[j] = word;
       word += (int64_t)(t.cube / sizeof(uint32_t));
       h_faceoff[j] = cells;
-      if (c.tiled || c.strip) cells += (int64_t)t.face;
+      if (c.tiled || c.strip || c.grid) cells += (int64_t)t.face;
     }
     h_off[3 * m] = pos;
     int32_t *d_scores = d_res, *d_final7 = d_res + m, *d_info = d_res + 8 * (size_t)m;
@@ -248,12 +267,12 @@ int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KPar
       rc = align_launch_tiled(d_seqs, d_off + 3 * (size_t)mr, c.n_over, pl.tymax, pl.tzmax, c.tile_pos, c.tile_lds, kp,
                               d_scores + mr, d_final7 + (size_t)NSTATE * mr, d_tb, d_tboff + mr, d_faces,
                               d_faceoff + mr, B.s);
-    else if (c.n_over && !c.strip)
+    else if (c.n_over && !c.strip && !c.grid)
       rc = plane_launch_batch(d_seqs, d_off + 3 * (size_t)mr, c.n_over, c.mla, c.mlb, c.mlc, kp, d_scores + mr,
                               d_final7 + (size_t)NSTATE * mr, d_ws, c.ws, B.s, d_tb, d_tboff + mr);
     if (rc) return rc;
-    // the strip triples are walked strip by strip below; every other one has its whole cube
-    const int32_t mw = c.strip ? mr : m;
+    // the strip and grid triples are walked segment by segment below; every other one has its whole cube
+    const int32_t mw = c.strip || c.grid ? mr : m;
     if (mw)
       hipLaunchKernelGGL(tb_walk_batch, dim3((mw + 63) / 64), dim3(64), 0, B.s, d_tb, d_tboff, d_off, mw, d_final7,
                          d_moves, d_info);
@@ -268,6 +287,23 @@ int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KPar
         if (j >= 0)
           hipLaunchKernelGGL(tb_walk_strip, dim3((c.n_over + 63) / 64), dim3(64), 0, B.s, d_tb, d_tboff + mr,
                              d_off + 3 * (size_t)mr, c.n_over, pl.tymax, pl.tzmax, j, d_final7 + (size_t)NSTATE * mr,
+                             d_walk, d_moves, d_info + 4 * (size_t)mr);
+      }
+    }
+    if (c.grid) {
+      // forward: diagonal by diagonal, every tile but the last of each triple;
+      // then the tile each walker stands in, followed by the walk of its pointers,
+      // as often as the longest path can change tiles
+      for (int32_t j = 0; j < 2 * c.max_diag - 1; ++j) {
+        const bool fwd = j < c.max_diag - 1;
+        const int32_t d = fwd ? j : j - (c.max_diag - 1);
+        if ((rc = align_launch_grid(d_seqs, d_off + 3 * (size_t)mr, c.n_over, pl.tymax, pl.tzmax, c.tile_pos,
+                                    c.tile_lds, kp, fwd, d, c.max_len, d_walk, d_scores + mr,
+                                    d_final7 + (size_t)NSTATE * mr, d_tb, d_tboff + mr, d_faces, d_faceoff + mr, B.s)))
+          return rc;
+        if (!fwd)
+          hipLaunchKernelGGL(tb_walk_grid, dim3((c.n_over + 63) / 64), dim3(64), 0, B.s, d_tb, d_tboff + mr,
+                             d_off + 3 * (size_t)mr, c.n_over, pl.tymax, pl.tzmax, d, d_final7 + (size_t)NSTATE * mr,
                              d_walk, d_moves, d_info + 4 * (size_t)mr);
       }
     }
@@ -317,6 +353,13 @@ int tsa_describe_align_plan(int32_t n, int32_t la, int32_t lb, int32_t lc, const
                16 * align_strip_face_cells(la, lb, lc, pl.tymax, pl.tzmax));
       break;
     }
+    case ALIGN_GRID: {
+      const AlignTileGeom g = align_tile_geom(lb, lc, pl.tymax, pl.tzmax);
+      snprintf(buf, len, "grid tile=%dx%d tiles=%dx%d lds=%zu cube=%zu faces=%zu", g.TY, g.TZ, g.nty, g.ntz,
+               align_resident_lds(la, g.TY, g.TZ), align_grid_cube_bytes(la, lb, lc, pl.tymax, pl.tzmax),
+               16 * align_grid_face_cells(la, lb, lc, pl.tymax, pl.tzmax));
+      break;
+    }
     default:
       snprintf(buf, len, "plane");
   }
@@ -326,10 +369,11 @@ int tsa_describe_align_plan(int32_t n, int32_t la, int32_t lb, int32_t lc, const
 }  // extern "C"
 
 namespace {
-// tsa_align_batch and tsa_align_batch_lowmem: validation, plan, budget, run.
-// lowmem: the plan mode is strip unless align_mode is set.
+// tsa_align_batch, tsa_align_batch_lowmem and tsa_align_batch_grid:
+// validation, plan, budget, run. unset: the plan mode unless align_mode is set
+// (auto, strip under lowmem, grid).
 int align_batch_entry(const uint8_t *seqs, const int64_t *offsets, int32_t n, const tsa_params *p, int32_t *scores,
-                      uint8_t *moves, int32_t *n_moves, int32_t *starts, int32_t device, bool lowmem) {
+                      uint8_t *moves, int32_t *n_moves, int32_t *starts, int32_t device, AlignMode unset) {
   if (!seqs || !offsets || !scores || !moves || !n_moves || !starts || n < 0 || !params_ok(p)) return TSA_EINVAL;
   for (int32_t i = 0; i < n; ++i) {
     const int64_t *o = offsets + 3 * (int64_t)i;
@@ -347,13 +391,14 @@ int align_batch_entry(const uint8_t *seqs, const int64_t *offsets, int32_t n, co
   if (rc) return rc;
   AlignPlan pl;
   if ((rc = align_plan_read(&pl))) return rc;
-  if (lowmem && !pl.mode_set) pl.mode = ALIGN_MODE_STRIP;
+  if (!pl.mode_set) pl.mode = unset;
   if (hipSetDevice(device) != hipSuccess) return TSA_EDEVICE;
   // The pointer-cube budget of a chunk: align_tb_bytes, or half of the device
   // memory free at the call (the other half is left to the caller's own
   // buffers and to the sequences, moves, plane rings and tile faces of the
   // chunk, all of which are O(N^2) against the cubes' O(N^3)). On the strip
-  // path a triple counts with its strip cube and its kept faces.
+  // path a triple counts with its strip cube and its kept faces, on the grid
+  // path with its tile cube and its kept faces.
   size_t budget = 0;
   long ov = 0;
   if (override_int("align_tb_bytes", &ov)) {
@@ -372,12 +417,17 @@ extern "C" {
 
 int tsa_align_batch(const uint8_t *seqs, const int64_t *offsets, int32_t n, const tsa_params *p,
                     int32_t *scores, uint8_t *moves, int32_t *n_moves, int32_t *starts, int32_t device) {
-  return align_batch_entry(seqs, offsets, n, p, scores, moves, n_moves, starts, device, false);
+  return align_batch_entry(seqs, offsets, n, p, scores, moves, n_moves, starts, device, ALIGN_MODE_AUTO);
 }
 
 int tsa_align_batch_lowmem(const uint8_t *seqs, const int64_t *offsets, int32_t n, const tsa_params *p,
                            int32_t *scores, uint8_t *moves, int32_t *n_moves, int32_t *starts, int32_t device) {
-  return align_batch_entry(seqs, offsets, n, p, scores, moves, n_moves, starts, device, true);
+  return align_batch_entry(seqs, offsets, n, p, scores, moves, n_moves, starts, device, ALIGN_MODE_STRIP);
+}
+
+int tsa_align_batch_grid(const uint8_t *seqs, const int64_t *offsets, int32_t n, const tsa_params *p,
+                         int32_t *scores, uint8_t *moves, int32_t *n_moves, int32_t *starts, int32_t device) {
+  return align_batch_entry(seqs, offsets, n, p, scores, moves, n_moves, starts, device, ALIGN_MODE_GRID);
 }
 
 // One triple, always by the plane sweep, with buffers and a one-thread walk of

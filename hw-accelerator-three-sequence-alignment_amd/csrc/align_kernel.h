@@ -1,7 +1,8 @@
 // align_kernel.h -- what the traceback entry points (align_api.hip) launch: the
 // resident kernel (align_kernel.hip), the tiled resident kernel
-// (align_tiled_kernel.hip), the strip kernel (align_strip_kernel.hip), the
-// batch form of the TB plane sweep and the batched walks (plane_kernel.hip).
+// (align_tiled_kernel.hip), the strip kernel (align_strip_kernel.hip), the grid
+// kernels (align_grid_kernel.hip), the batch form of the TB plane sweep and the
+// batched walks (plane_kernel.hip).
 #pragma once
 
 #include "tsa_internal.h"
@@ -107,5 +108,40 @@ int align_launch_strip(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t 
 __global__ void tb_walk_strip(const uint32_t *tb, const int64_t *tb_off, const int64_t *offs, int32_t n,
                               int32_t tymax, int32_t tzmax, int32_t j, const int32_t *final7, int32_t *walk,
                               uint8_t *moves, int32_t *info);
+
+// The grid kernels (align_grid_kernel.hip): the tiled kernel's tiles, every one
+// checkpointed. Forward launch d sweeps the tiles with ty + tz = d of every
+// triple, one workgroup each, and keeps the y face of every tile row but the
+// last and the z face of every tile column but the last; backward launch j then
+// sweeps again, with pointers into a cube of one tile, the tile the triple's
+// walker stands in, up to the walker's x, and tb_walk_grid follows them before
+// launch j+1 overwrites it.
+// Bytes of a triple's tile cube, TY*(la+TZ-1)*TZ words.
+size_t align_grid_cube_bytes(int32_t la, int32_t lb, int32_t lc, int32_t tymax, int32_t tzmax);
+// 16-byte cells of its kept faces: nty-1 y faces [la][lc+1] and ntz-1 z faces
+// [la][lb]. A grid triple's need against the budget is the sum of both:
+//   4*TY*(la+TZ-1)*TZ + 16*((nty-1)*la*(lc+1) + (ntz-1)*la*lb)  bytes.
+size_t align_grid_face_cells(int32_t la, int32_t lb, int32_t lc, int32_t tymax, int32_t tzmax);
+// One launch through launch_with_lds. fwd: launch d of the forward form over
+// (n triples) x (ndiag indices along the diagonal, the most tiles any triple
+// has on one); a workgroup without a tile on diagonal d, or with the last tile,
+// leaves at once. Otherwise launch d of the backward form, one workgroup per
+// triple, which skips a triple whose record in d_walk is done (d = 0 reads no
+// record: the tile of (lb,lc), all of x). max_pos, lds and d_face_off as
+// align_launch_tiled's, over align_grid_face_cells; d_tb_off[t] = the word
+// offset of triple t's tile cube.
+int align_launch_grid(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, int32_t tymax, int32_t tzmax,
+                      int64_t max_pos, size_t lds, const KParams &kp, bool fwd, int32_t d, int32_t ndiag,
+                      const int32_t *d_walk, int32_t *d_scores, int32_t *d_final7, uint32_t *d_tb,
+                      const int64_t *d_tb_off, void *d_faces, const int64_t *d_face_off, hipStream_t stream);
+// The walk after backward launch j, one walker (thread) per triple: it follows
+// the pointers of the tile its record stands in (from (la,lb,lc) and final7
+// when j = 0) while the cell lies in that tile, appending to moves[offs[3t] ..)
+// from the end backwards. A predecessor on a zero face ends the path as in
+// tb_walk_strip; one in another tile -- through a y seam, a z seam or the
+// corner -- saves the record for launch j+1.
+__global__ void tb_walk_grid(const uint32_t *tb, const int64_t *tb_off, const int64_t *offs, int32_t n,
+                             int32_t tymax, int32_t tzmax, int32_t j, const int32_t *final7, int32_t *walk,
+                             uint8_t *moves, int32_t *info);
 
 }  // namespace tsa

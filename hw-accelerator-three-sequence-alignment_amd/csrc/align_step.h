@@ -2,8 +2,8 @@
 // and the lookup of A's symbols, the register state of a (y,z) position and
 // one step of the schedule for it. align_kernel.hip explains the schedule and
 // calls the step with its whole plane as the one tile; align_tiled_kernel.hip
-// and align_strip_kernel.hip call it tile by tile, the forward form of the
-// latter without the pointer word. The cell is literal_cell.h's max7_literal on the
+// align_strip_kernel.hip and align_grid_kernel.hip call it tile by tile, the
+// forward forms of the latter two without the pointer word. The cell is literal_cell.h's max7_literal on the
 // plane sweep's operands (src/PE_1cyc.v:159-218, MAX7 src/PE_1cyc.v:1-32).
 //
 // Both kernels sit at the SGPR limit, where one more SGPR is a spilled VGPR, and
@@ -66,12 +66,20 @@ struct AlignPos {
   // 0 <= x = q-y-z <= la reads rd = buf[(q-1)&1] (row stride ldz) and, while
   // x >= 1, publishes its cell into wr = buf[q&1], stores its pointer word in
   // cube and, at the cube's end (la,lb,lc), the triple's score and final states.
-  // TB = false (the forward form of align_strip_kernel.hip): the cells alone,
-  // no argmax, no pointer word, no score.
+  // TB = false (the forward forms of align_strip_kernel.hip and
+  // align_grid_kernel.hip): the cells alone, no argmax, no pointer word, no
+  // score. cld: the words of a row of the cube, tb_index's lc -- lc itself
+  // unless the cube holds one tile (align_grid_kernel.hip).
   template <bool TB = true, class SymA>
   __device__ __forceinline__ void step(const uint4 *rd, uint4 *wr, int32_t ldz, int32_t q, int32_t la, int32_t y0,
                                        int32_t z0, int32_t lb, int32_t lc, uint32_t *cube, const KParams &kp,
                                        int64_t t, int32_t *scores, int32_t *final7, const SymA &symA) {
+    step<TB>(rd, wr, ldz, q, la, y0, z0, lb, lc, cube, kp, t, scores, final7, symA, lc);
+  }
+  template <bool TB = true, class SymA>
+  __device__ __forceinline__ void step(const uint4 *rd, uint4 *wr, int32_t ldz, int32_t q, int32_t la, int32_t y0,
+                                       int32_t z0, int32_t lb, int32_t lc, uint32_t *cube, const KParams &kp,
+                                       int64_t t, int32_t *scores, int32_t *final7, const SymA &symA, int32_t cld) {
     const int32_t sh = kp.wrap_shift;
     const int32_t y = (int32_t)(meta & 0x1FFFu), z = (int32_t)((meta >> 13) & 0x1FFFu);
     const int32_t x = q - y - z;
@@ -104,7 +112,7 @@ struct AlignPos {
         w |= g << (3 * SIZ);
         wr[idx] = pack7(S);
         if constexpr (TB) {
-          cube[tb_index(x, y0 + y, z0 + z, la, lc)] = w;
+          cube[tb_index(x, y0 + y, z0 + z, la, cld)] = w;
           if (x == la && y0 + y == lb && z0 + z == lc) {  // FINAL_MAX, src/TriAlign_1cyc.v:141-142
             int32_t m = S[0];
 #pragma unroll

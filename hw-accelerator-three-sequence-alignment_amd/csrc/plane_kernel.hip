@@ -348,6 +348,67 @@ __global__ __launch_bounds__(64) void tb_walk_strip(const uint32_t *__restrict__
   }
 }
 
+// The walk of one tile (align_grid_kernel.hip) per triple, after backward
+// launch j: tb_walk_strip's segments, bounded by a tile instead of a strip.
+// The cube holds the tile of the record's cell alone, swept up to the record's
+// x = xm, cell (x,y,z) at tb_index(x, y - y0, z - z0, xm, TZ): the walker reads
+// a pointer only while y > y0 and z > z0 and saves the record when the
+// predecessor lies in another tile -- beyond the y seam, the z seam or both
+// (the corner). Every segment lowers ty + tz of the walker's tile, and tile
+// (0,0) ends on a zero face at the latest, so nty + ntz - 1 launches finish
+// every walker.
+__global__ __launch_bounds__(64) void tb_walk_grid(const uint32_t *__restrict__ tb,
+                                                   const int64_t *__restrict__ tb_off,
+                                                   const int64_t *__restrict__ offs, int32_t n, int32_t tymax,
+                                                   int32_t tzmax, int32_t j, const int32_t *__restrict__ final7,
+                                                   int32_t *__restrict__ walk, uint8_t *__restrict__ moves,
+                                                   int32_t *__restrict__ info) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const int64_t o0 = offs[3 * t], o1 = offs[3 * t + 1], o2 = offs[3 * t + 2], o3 = offs[3 * t + 3];
+  const int32_t la = (int32_t)(o1 - o0), lb = (int32_t)(o2 - o1), lc = (int32_t)(o3 - o2);
+  const AlignTileGeom tg = align_tile_geom(lb, lc, tymax, tzmax);
+  int32_t *rec = walk + ALIGN_WALK_REC * t;
+  if (j > 0 && rec[5]) return;
+  int32_t x, y, z, T, m;
+  if (j == 0) {  // final MAX7 (src/TriAlign_1cyc.v:141-142): lowest state index on ties
+    const int32_t *f7 = final7 + t * NSTATE;
+    T = 0;
+    for (int k = 1; k < NSTATE; ++k)
+      if (f7[k] > f7[T]) T = k;
+    x = la, y = lb, z = lc, m = 0;
+  } else {
+    x = rec[0], y = rec[1], z = rec[2], T = rec[3], m = rec[4];
+  }
+  constexpr int DX[7] = {1, 1, 0, 0, 1, 0, 1}, DY[7] = {1, 0, 1, 0, 1, 1, 0},
+                DZ[7] = {1, 0, 0, 1, 0, 1, 1};  // predecessor offsets per state
+  const uint32_t *cube = tb + tb_off[t];
+  const int32_t xm = x;                                                    // the sweep stopped here
+  const int32_t y0 = (y - 1) / tg.TY * tg.TY, z0 = (z - 1) / tg.TZ * tg.TZ;  // the rows and columns before the tile
+  uint8_t *mv = moves + o0;
+  int32_t done = 0;
+  for (;;) {
+    mv[m++] = (uint8_t)T;
+    const int32_t px = x - DX[T], py = y - DY[T], pz = z - DZ[T];
+    if (px == 0 || py == 0 || pz == 0 || m >= la + lb + lc) {
+      x = px, y = py, z = pz;
+      done = 1;
+      break;
+    }
+    T = (int32_t)((cube[tb_index(x, y - y0, z - z0, xm, tg.TZ)] >> (3 * T)) & 7u);
+    x = px, y = py, z = pz;
+    if (y <= y0 || z <= z0) break;  // another tile: launch j+1 sweeps it
+  }
+  rec[0] = x, rec[1] = y, rec[2] = z, rec[3] = T, rec[4] = m, rec[5] = done;
+  if (!done) return;
+  info[4 * t] = m, info[4 * t + 1] = x, info[4 * t + 2] = y, info[4 * t + 3] = z;
+  for (int32_t i = 0, k = m - 1; i < k; ++i, --k) {
+    const uint8_t v = mv[i];
+    mv[i] = mv[k];
+    mv[k] = v;
+  }
+}
+
 size_t tb_cube_bytes(int32_t la, int32_t lb, int32_t lc) {
   return (size_t)lb * (size_t)(la + lc - 1) * (size_t)lc * sizeof(uint32_t);
 }

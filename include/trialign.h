@@ -289,13 +289,42 @@ int tsa_align_batch_lowmem(const uint8_t *seqs, const int64_t *offsets, int32_t 
                            const tsa_params *p, int32_t *scores, uint8_t *moves,
                            int32_t *n_moves, int32_t *starts, int32_t device);
 
+/* tsa_align_batch with the larger triples on the grid path: the same
+ * signature, validation, error codes, thread safety and results, move for
+ * move, with the plan mode grid unless the override align_mode is set (a set
+ * override holds, as under tsa_align_batch_lowmem). Triples that fit one
+ * workgroup stay with the resident kernel and a whole cube. Every other triple
+ * is cut into the tiled kernel's tiles (the same caps and align_tile override;
+ * nty x ntz tiles of TY x TZ), and the last row and the last column of every
+ * tile are kept: nty-1 y faces [la][lc+1] and ntz-1 z faces [la][lb]. Forward
+ * launch d = 0 .. nty+ntz-3 sweeps the tiles with ty + tz = d without pointers,
+ * one workgroup per tile -- tiles of one diagonal are independent, and stream
+ * order is all that orders the launches. Backward launch j = 0, 1, .. then
+ * sweeps again, with pointers into a cube of one tile, only the tile the
+ * triple's walker stands in, and of it only x up to the walker's x; a walk
+ * launch follows the pointers until the path leaves the tile -- through a y
+ * seam, a z seam or the corner -- or ends. A path visits at most nty+ntz-1
+ * tiles. Per grid triple the need is
+ *   4*TY*(la+TZ-1)*TZ + 16*((nty-1)*la*(lc+1) + (ntz-1)*la*lb)  bytes
+ * (tile cube + kept faces, both counted against the budget; the full cube for
+ * a resident triple). A chunk holds consecutive triples whose needs fit the
+ * budget, and TSA_ENOMEM is returned only when one triple's own need exceeds
+ * it. A chunk queues [resident] + max (nty+ntz-2) forward + max (nty+ntz-1)
+ * backward counted launches (tsa_kernel_launch_count), the maxima over its
+ * grid triples. */
+int tsa_align_batch_grid(const uint8_t *seqs, const int64_t *offsets, int32_t n,
+                         const tsa_params *p, int32_t *scores, uint8_t *moves,
+                         int32_t *n_moves, int32_t *starts, int32_t device);
+
 /* Which path tsa_align_batch takes for a group (one chunk) of n triples of
  * these lengths under the current overrides, as a short text that begins with
- * "resident", "tiled", "strip" or "plane"; for tiled it carries the tile and
+ * "resident", "tiled", "strip", "grid" or "plane"; for tiled it carries the tile and
  * the tile grid, such as "tiled tile=64x43 tiles=4x6 lds=91632 faces=5259264"
  * (lds: dynamic LDS of the workgroup, faces: bytes of the triple's face
  * workspace), for strip also the bytes of the strip cube, such as
- * "strip tile=7x7 tiles=3x3 lds=2080 cube=16240 faces=8960".
+ * "strip tile=7x7 tiles=3x3 lds=2080 cube=16240 faces=8960", for grid the
+ * bytes of the tile cube and of the kept faces, such as
+ * "grid tile=7x7 tiles=3x3 lds=2080 cube=3136 faces=13120".
  * It is built from the functions the dispatch uses. Host-only, no device
  * needed. TSA_EINVAL for a null or empty buffer, n or a length below 1, bad
  * parameters, or an align_mode / align_tile value that is not valid. */
@@ -325,7 +354,8 @@ int64_t tsa_check_fallback_count(void);
 /* Kernel launches with dynamic LDS (helix, lap, literal helix; the resident
  * and the tiled resident traceback kernel of tsa_align_batch, each one per
  * chunk that has triples for it; the forward and the strip launches of the
- * strip path) the library has queued
+ * strip path; the forward launches, one per diagonal of the tile grid, and the
+ * backward launches of the grid path) the library has queued
  * since it was loaded: a call that reuses an error left over from an earlier
  * HIP call must still launch its kernel exactly once (tests). The plane sweep
  * and the traceback walks are not counted. */
@@ -359,14 +389,15 @@ const char *tsa_version(void);
  *   lap_spin_limit  polls before a lap hand-off times out (0: at once)
  *   lap_trace       path of a per-workgroup timestamp CSV (tools/lap_trace.py)
  *   split_serial    0 | 1           (tsa_score_gpu_multi parts one by one)
- *   align_mode      resident | plane | tiled | strip (tsa_align_batch: resident
+ *   align_mode      resident | plane | tiled | strip | grid (tsa_align_batch: resident
  *                   still sends a triple that does not fit a workgroup to the
  *                   plane sweep; tiled sends it to the tiled resident kernel,
- *                   strip to the strip path of tsa_align_batch_lowmem, and
- *                   under either no triple takes the plane sweep)
+ *                   strip to the strip path of tsa_align_batch_lowmem, grid
+ *                   to the grid path of tsa_align_batch_grid, and under any
+ *                   of the three no triple takes the plane sweep)
  *   align_tb_bytes  pointer-cube budget of a tsa_align_batch chunk, in bytes
  *   align_tile      TYxTZ, e.g. 5x7: caps the tile edges of the tiled kernel;
- *                   under align_mode = tiled or strip every triple larger than
+ *                   under align_mode = tiled, strip or grid every triple larger than
  *                   the tile is tiled, even one that would fit a workgroup. A malformed
  *                   value, an edge below 1 or a tile over the tiled kernel's
  *                   capacity (the resident capacity, and TY*TZ <= 3072) makes tsa_align_batch and tsa_describe_align_plan return

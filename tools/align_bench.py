@@ -9,8 +9,10 @@ synchronous, so host wall time is the time a caller waits.
   python tools/align_bench.py --n 256 --la 256 --forms tiled,plane
   python tools/align_bench.py --n 256 --la 256 --forms tiled,strip
   python tools/align_bench.py --n 8 --la 512 --forms tiled,strip --tb-bytes 1073741824
+  python tools/align_bench.py --n 8 --la 512 --forms tiled,strip,grid --tb-bytes 536870912
+  python tools/align_bench.py --n 1 --la 1024 --forms strip,grid --passes 1 --warmup 0
 (a form other than loop is passed to align_mode as it stands: resident, plane,
-tiled or strip; --tb-bytes sets align_tb_bytes for every batch form, and a form
+tiled, strip or grid; --tb-bytes sets align_tb_bytes for every batch form, and a form
 the library refuses, such as tiled with a cube over that budget, is recorded
 with its error instead of a time).
 A library without tsa_align_batch (an older build named by TSA_PKG_DIR) runs
@@ -38,7 +40,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--loop-n", type=int, default=None, help="triples of the align loop (default: all)")
     ap.add_argument("--forms", default="resident,plane,loop",
-                    help="comma list of loop and align_mode values: resident, plane, tiled, strip")
+                    help="comma list of loop and align_mode values: resident, plane, tiled, strip, grid")
     ap.add_argument("--tb-bytes", type=int, default=None, help="align_tb_bytes of the batch forms")
     args = ap.parse_args()
     import bench
