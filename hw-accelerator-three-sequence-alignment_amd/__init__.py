@@ -65,7 +65,7 @@ EXPORTS = (
     "tsa_fallback_count", "tsa_check_fallback_count", "tsa_score_batch_async_p2", "tsa_pack2",
     "tsa_score_gpu_multi", "tsa_score_batch_devices", "tsa_set_override", "tsa_get_overrides",
     "tsa_kernel_launch_count", "tsa_align_batch", "tsa_describe_align_plan", "tsa_align_batch_lowmem",
-    "tsa_align_batch_grid",
+    "tsa_align_batch_grid", "tsa_align_workspace_size", "tsa_align_batch_async", "tsa_align_rows_async",
 )
 
 # Plan overrides the library accepts (tsa_set_override; include/trialign.h).
@@ -81,6 +81,12 @@ SCORE_UNCERTIFIED = -(2 ** 31) + 1
 # (A, B, C) it consumes -- the predecessor offsets of src/PE_1cyc.v:164-218.
 MOVES = ("M", "Ix", "Iy", "Iz", "Ixy", "Iyz", "Ixz")
 MOVE_CONSUMES = ((1, 1, 1), (1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (0, 1, 1), (1, 0, 1))
+
+# The path of the larger triples in tsa_align_batch_async (TSA_ALIGN_PATH_*).
+ALIGN_PATHS = {"tiled": 0, "strip": 1, "grid": 2}
+# Codes of tsa_align_rows_async: ROW_LETTERS[code], TSA_ROW_GAP = 5.
+ROW_GAP = 5
+ROW_LETTERS = "ATCGN-"
 
 
 class TsaParams(ctypes.Structure):
@@ -150,6 +156,14 @@ def _load_lib() -> ctypes.CDLL:
                                     ctypes.c_int32]
     lib.tsa_align_batch_lowmem.argtypes = lib.tsa_align_batch.argtypes
     lib.tsa_align_batch_grid.argtypes = lib.tsa_align_batch.argtypes
+    szp = ctypes.POINTER(ctypes.c_size_t)
+    lib.tsa_align_workspace_size.argtypes = [i64p, ctypes.c_int32, pp, ctypes.c_int32, szp, szp]
+    lib.tsa_align_batch_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, i64p, ctypes.c_int32, pp,
+                                          ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_size_t, ctypes.c_void_p]
+    lib.tsa_align_rows_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32] + \
+        [ctypes.c_void_p] * 5
     lib.tsa_score_gpu_multi.argtypes = [u8p, ctypes.c_int32, u8p, ctypes.c_int32, u8p,
                                         ctypes.c_int32, pp, i32p, ctypes.c_int32, i32p,
                                         ctypes.POINTER(ctypes.c_double)]
@@ -173,7 +187,8 @@ def _load_lib() -> ctypes.CDLL:
                  "tsa_describe_plan", "tsa_align_gpu", "tsa_score_batch_async_p2", "tsa_pack2",
                  "tsa_score_gpu_multi", "tsa_score_batch_devices", "tsa_set_override",
                  "tsa_get_overrides", "tsa_align_batch", "tsa_describe_align_plan",
-                 "tsa_align_batch_lowmem", "tsa_align_batch_grid"):
+                 "tsa_align_batch_lowmem", "tsa_align_batch_grid", "tsa_align_workspace_size",
+                 "tsa_align_batch_async", "tsa_align_rows_async"):
         getattr(lib, name).restype = ctypes.c_int
     return lib
 
@@ -256,8 +271,9 @@ class overrides:
 
 def kernel_launch_count() -> int:
     """Scoring-kernel launches (and resident / tiled resident traceback
-    launches, one each per align_batch chunk) queued since the library was
-    loaded."""
+    launches, one each per align_batch chunk; the helper kernels of
+    align_batch_async and align_rows_async are not counted) queued since the
+    library was loaded."""
     return int(_lib.tsa_kernel_launch_count())
 
 
@@ -580,6 +596,98 @@ def score_batch_async(d_seqs_ptr: int, d_offsets_ptr: int, n: int, max_la: int, 
                                     ctypes.c_void_p(d_scores_ptr), ctypes.c_void_p(d_ws_ptr),
                                     ctypes.c_size_t(ws_bytes), ctypes.c_void_p(stream_ptr))
     _check(rc, "tsa_score_batch_async")
+
+
+def _align_path(path) -> int:
+    return ALIGN_PATHS[path] if isinstance(path, str) else int(path)
+
+
+def align_workspace_size(offsets, params: Optional[TsaParams] = None, path: str | int = "tiled") -> tuple:
+    """tsa_align_workspace_size: ``(min_bytes, full_bytes)`` of the workspace
+    of ``align_batch_async`` for the batch with these (host) offsets --
+    the smallest size the call succeeds with, and the size from which it takes
+    the fewest chunks. Host-only. ``path``: "tiled", "strip" or "grid"."""
+    p = params or TsaParams.default()
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = (len(offsets) - 1) // 3
+    lo, hi = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(_lib.tsa_align_workspace_size(_ptr(offsets, ctypes.c_int64), n, ctypes.byref(p), _align_path(path),
+                                         ctypes.byref(lo), ctypes.byref(hi)), "tsa_align_workspace_size")
+    return int(lo.value), int(hi.value)
+
+
+def align_batch_async(d_seqs_ptr: int, d_offsets_ptr: int, offsets, d_scores_ptr: int, d_moves_ptr: int,
+                      d_n_moves_ptr: int, d_starts_ptr: int, d_ws_ptr: int, ws_bytes: int,
+                      stream_ptr: int = 0, params: Optional[TsaParams] = None, path: str | int = "tiled") -> None:
+    """Device-resident traceback (tsa_align_batch_async): queues the alignment
+    of the batch on the stream and returns. Pointers are raw device addresses
+    (e.g. ``tensor.data_ptr()``), ``offsets`` the host copy of the 3n+1 offsets
+    at ``d_offsets_ptr``; outputs in ``align_batch``'s layout, workspace of at
+    least ``align_workspace_size(...)[0]`` bytes, 256-byte aligned."""
+    p = params or TsaParams.default()
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = (len(offsets) - 1) // 3
+    rc = _lib.tsa_align_batch_async(ctypes.c_void_p(d_seqs_ptr), ctypes.c_void_p(d_offsets_ptr),
+                                    _ptr(offsets, ctypes.c_int64), n, ctypes.byref(p), _align_path(path),
+                                    ctypes.c_void_p(d_scores_ptr), ctypes.c_void_p(d_moves_ptr),
+                                    ctypes.c_void_p(d_n_moves_ptr), ctypes.c_void_p(d_starts_ptr),
+                                    ctypes.c_void_p(d_ws_ptr), ctypes.c_size_t(ws_bytes),
+                                    ctypes.c_void_p(stream_ptr))
+    _check(rc, "tsa_align_batch_async")
+
+
+def align_rows_async(d_seqs_ptr: int, d_offsets_ptr: int, n: int, d_moves_ptr: int, d_n_moves_ptr: int,
+                     d_starts_ptr: int, d_rows_ptr: int, stream_ptr: int = 0) -> None:
+    """The gapped rows of ``n`` alignments on the device (tsa_align_rows_async):
+    three rows of la+lb+lc bytes per triple at ``3 * (offsets[3i] -
+    offsets[0])``, codes ``ROW_LETTERS[code]``, the first n_moves[i] of each
+    row written."""
+    rc = _lib.tsa_align_rows_async(ctypes.c_void_p(d_seqs_ptr), ctypes.c_void_p(d_offsets_ptr), n,
+                                   ctypes.c_void_p(d_moves_ptr), ctypes.c_void_p(d_n_moves_ptr),
+                                   ctypes.c_void_p(d_starts_ptr), ctypes.c_void_p(d_rows_ptr),
+                                   ctypes.c_void_p(stream_ptr))
+    _check(rc, "tsa_align_rows_async")
+
+
+def align_batch_device(d_seqs, offsets, params: Optional[TsaParams] = None, path: str | int = "tiled",
+                       workspace=None, rows: bool = False, stream=None):
+    """``align_batch`` for sequences that are already on the device: ``d_seqs``
+    a CUDA ``uint8`` torch tensor holding the batch buffer, ``offsets`` the
+    host offsets (3n+1) into it. Allocates the outputs and, unless
+    ``workspace`` (a CUDA ``uint8`` tensor) is given, a ``full_bytes``
+    workspace as torch tensors, queues the work on ``stream`` (default: torch's
+    current stream) and returns the tensors ``(scores, moves, n_moves,
+    starts)`` -- with ``rows=True`` also the gapped rows of
+    ``align_rows_async`` -- without synchronising. Layouts as ``align_batch``'s
+    (``moves`` and ``rows`` relative to ``offsets[0]``); ``n_moves[i] == 0``
+    flags a triple whose walk failed."""
+    import torch as _torch
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = (len(offsets) - 1) // 3
+    if not (d_seqs.is_cuda and d_seqs.dtype == _torch.uint8 and d_seqs.is_contiguous()):
+        raise TsaError(TSA_EINVAL, "d_seqs must be a contiguous CUDA uint8 tensor")
+    dev = d_seqs.device
+    st = stream if stream is not None else _torch.cuda.current_stream(dev)
+    total = int(offsets[-1] - offsets[0]) if n else 0
+    with _torch.cuda.stream(st):
+        d_off = _torch.from_numpy(offsets).to(dev)
+        scores = _torch.zeros(max(n, 1), dtype=_torch.int32, device=dev)
+        n_moves = _torch.zeros(max(n, 1), dtype=_torch.int32, device=dev)
+        starts = _torch.zeros(max(3 * n, 1), dtype=_torch.int32, device=dev)
+        moves = _torch.zeros(max(total, 1), dtype=_torch.uint8, device=dev)
+        if workspace is None:
+            workspace = _torch.empty(max(align_workspace_size(offsets, params, path)[1], 256),
+                                     dtype=_torch.uint8, device=dev)
+        align_batch_async(d_seqs.data_ptr(), d_off.data_ptr(), offsets, scores.data_ptr(), moves.data_ptr(),
+                          n_moves.data_ptr(), starts.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                          st.cuda_stream, params, path)
+        out = (scores[:n], moves[:total], n_moves[:n], starts[:3 * n])
+        if rows:
+            d_rows = _torch.full((max(3 * total, 1),), ROW_GAP, dtype=_torch.uint8, device=dev)
+            align_rows_async(d_seqs.data_ptr(), d_off.data_ptr(), n, moves.data_ptr(), n_moves.data_ptr(),
+                             starts.data_ptr(), d_rows.data_ptr(), st.cuda_stream)
+            out += (d_rows[:3 * total],)
+    return out
 
 
 def pack2(seqs) -> np.ndarray:

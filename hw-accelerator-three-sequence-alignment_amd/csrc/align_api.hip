@@ -1,6 +1,9 @@
 // align_api.hip -- the traceback entry points of include/trialign.h:
 // tsa_align_batch, tsa_align_batch_lowmem, tsa_align_batch_grid, tsa_align_gpu
-// (one triple, always the plane sweep) and tsa_describe_align_plan. Host code
+// (one triple, always the plane sweep), tsa_describe_align_plan and the
+// device-resident tsa_align_workspace_size, tsa_align_batch_async and
+// tsa_align_rows_async, which plan with the same planner against a caller's
+// workspace and queue the same launches (helper kernels: align_async_kernel.hip). Host code
 // only: which path a triple takes, the chunks of pointer cubes, the device buffers and the
 // launches of the resident kernel (align_kernel.hip), the tiled resident kernel
 // (align_tiled_kernel.hip), the strip kernel (align_strip_kernel.hip), the grid
@@ -57,15 +60,6 @@ struct AlignBufs {
 // tile grid as workgroups of their own and sweeps again, with the pointers of
 // one tile, only the tiles on the path: opt-in as well.
 enum AlignPath { ALIGN_RESIDENT, ALIGN_TILED, ALIGN_PLANE, ALIGN_STRIP, ALIGN_GRID };
-enum AlignMode {
-  ALIGN_MODE_AUTO, ALIGN_MODE_RESIDENT, ALIGN_MODE_PLANE, ALIGN_MODE_TILED, ALIGN_MODE_STRIP, ALIGN_MODE_GRID
-};
-struct AlignPlan {
-  AlignMode mode = ALIGN_MODE_AUTO;
-  bool mode_set = false;  // align_mode is set
-  bool capped = false;  // align_tile is set
-  int32_t tymax = ALIGN_TILE_Y, tzmax = ALIGN_TILE_Z;
-};
 // 256 = the smallest measured group from which the tiled kernel's median beat the
 // plane sweep's beyond the spread of the passes on every shape (128^3 and 256^3;
 // at 64 triples the plane sweep still wins both): one workgroup per CU.
@@ -100,15 +94,6 @@ int align_plan_read(AlignPlan *pl) {
     pl->tymax = (int32_t)e[0], pl->tzmax = (int32_t)e[1];
   }
   return TSA_OK;
-}
-
-// Over capacity: the triple does not go to the resident kernel as a whole.
-// With align_tile set under align_mode = tiled, strip or grid that is any triple
-// larger than the tile (tests put tiny cubes through many tiles that way).
-bool align_over(const AlignPlan &pl, int32_t la, int32_t lb, int32_t lc) {
-  if ((pl.mode == ALIGN_MODE_TILED || pl.mode == ALIGN_MODE_STRIP || pl.mode == ALIGN_MODE_GRID) && pl.capped)
-    return lb > pl.tymax || lc > pl.tzmax;
-  return !align_resident_fits(la, lb, lc);
 }
 
 // The path of the over-capacity triples of a group that holds n_over of them.
@@ -153,39 +138,40 @@ struct AlignChunk {
   size_t ws = 0;
 };
 
-// The traceback of n validated triples on the current device: plan pl, chunks
-// of at most `budget` bytes of pointer cubes. Outputs as tsa_align_batch's.
-int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KParams &kp, const AlignPlan &pl,
-              size_t budget, int32_t *scores, uint8_t *moves, int32_t *n_moves, int32_t *starts) {
+// The plan of n validated triples under pl, from (a host copy of) their
+// offsets. tiled_faces: a tiled triple's face workspace counts against the
+// budget as well (tsa_align_batch_async, whose faces and cubes share one
+// workspace; the synchronous entry points allocate the tiled faces apart).
+std::vector<AlignTriple> align_plan_triples(const int64_t *offsets, int32_t n, const AlignPlan &pl, bool tiled_faces) {
   std::vector<AlignTriple> T((size_t)n);
   for (int32_t i = 0; i < n; ++i) {
     const int64_t *o = offsets + 3 * (int64_t)i;
     AlignTriple &t = T[i];
     t.la = (int32_t)(o[1] - o[0]), t.lb = (int32_t)(o[2] - o[1]), t.lc = (int32_t)(o[3] - o[2]);
-    t.over = align_path(pl, t.la, t.lb, t.lc, 0) != ALIGN_RESIDENT;
-    const bool strip = t.over && pl.mode == ALIGN_MODE_STRIP, grid = t.over && pl.mode == ALIGN_MODE_GRID;
-    t.cube = strip  ? align_strip_cube_bytes(t.la, t.lb, t.lc, pl.tymax, pl.tzmax)
-             : grid ? align_grid_cube_bytes(t.la, t.lb, t.lc, pl.tymax, pl.tzmax)
-                    : tb_cube_bytes(t.la, t.lb, t.lc);
+    const AlignNeed nd = align_need(pl, t.la, t.lb, t.lc);
+    t.over = nd.over, t.cube = nd.cube, t.face = nd.face;
+    const bool kept = t.over && (pl.mode == ALIGN_MODE_STRIP || pl.mode == ALIGN_MODE_GRID || tiled_faces);
     const AlignTileGeom g = t.over ? align_tile_geom(t.lb, t.lc, pl.tymax, pl.tzmax) : AlignTileGeom{t.lb, t.lc, 1, 1};
-    t.face = strip    ? align_strip_face_cells(t.la, t.lb, t.lc, pl.tymax, pl.tzmax)
-             : grid   ? align_grid_face_cells(t.la, t.lb, t.lc, pl.tymax, pl.tzmax)
-             : t.over ? align_tiled_face_cells(t.la, t.lb, t.lc, pl.tymax, pl.tzmax)
-                      : 0;
-    t.need = t.cube + (strip || grid ? sizeof(uint4) * t.face : 0);
+    t.need = t.cube + (kept ? sizeof(uint4) * t.face : 0);
     t.nty = g.nty, t.ntz = g.ntz;
     t.pos = (int64_t)g.TY * g.TZ;
     t.lds = align_resident_lds(t.la, g.TY, g.TZ);
   }
-  std::vector<AlignChunk> chunks;
-  size_t max_cube = 0, max_seq = 0, max_ws = 0, max_face = 0;
-  int32_t max_n = 0;
+  return T;
+}
+
+// The chunks of the planned triples T: consecutive triples whose needs fit
+// `budget` together, at most 65535. TSA_ENOMEM when one triple's own need
+// exceeds the budget, as a failed allocation.
+int align_plan_chunks(const std::vector<AlignTriple> &T, const AlignPlan &pl, size_t budget,
+                      std::vector<AlignChunk> *chunks) {
+  const int32_t n = (int32_t)T.size();
   for (int32_t i = 0; i < n;) {
     AlignChunk c;  // the over-capacity triples' needs for both of their paths, until their number decides
     int32_t j = i;
     for (; j < n && j - i < 65535; ++j) {
       const AlignTriple &t = T[j];
-      if (t.need > budget) return TSA_ENOMEM;  // one triple over the budget, as a failed allocation
+      if (t.need > budget) return TSA_ENOMEM;
       if (t.need > budget - c.need) break;
       c.need += t.need;
       c.cube += t.cube;
@@ -207,11 +193,95 @@ int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KPar
     c.grid = c.n_over && align_over_path(pl, c.n_over) == ALIGN_GRID;
     if (!c.tiled && !c.strip && !c.grid)
       c.face = 0, c.ws = c.n_over ? plane_workspace_bytes(c.n_over, c.mla, c.mlb, c.mlc) : 0;
-    chunks.push_back(c);
+    chunks->push_back(c);
+    i = j;
+  }
+  return TSA_OK;
+}
+
+// The device buffers of one chunk as its launches see them: the sequences
+// packed in launch order -- the resident triples first, then the over-capacity
+// ones (tiled, plane, strip or grid, one path for all of a chunk), so each path
+// sees a contiguous sub-batch -- with their offsets, cube word offsets and face
+// cell offsets, the results (m scores, 7m final states, 4m walk infos) and the
+// moves, laid out as the sequences.
+struct AlignDev {
+  const uint8_t *seqs;
+  const int64_t *off, *tboff, *faceoff;
+  int32_t *scores, *final7, *info;
+  uint8_t *moves;
+  uint32_t *tb;
+  void *faces, *ws;
+  int32_t *walk;  // the walker records of a chunk's strip or grid triples
+};
+
+// Queues the sweeps and walks of chunk c on stream s.
+int align_queue_chunk(const AlignChunk &c, const AlignPlan &pl, const KParams &kp, const AlignDev &d, hipStream_t s) {
+  const int32_t m = c.i1 - c.i0, mr = m - c.n_over;
+  int rc = TSA_OK;
+  if (mr && (rc = align_launch_resident(d.seqs, d.off, mr, c.max_pos, c.lds, kp, d.scores, d.final7, d.tb, d.tboff, s)))
+    return rc;
+  if (c.tiled)
+    rc = align_launch_tiled(d.seqs, d.off + 3 * (size_t)mr, c.n_over, pl.tymax, pl.tzmax, c.tile_pos, c.tile_lds, kp,
+                            d.scores + mr, d.final7 + (size_t)NSTATE * mr, d.tb, d.tboff + mr, d.faces,
+                            d.faceoff + mr, s);
+  else if (c.n_over && !c.strip && !c.grid)
+    rc = plane_launch_batch(d.seqs, d.off + 3 * (size_t)mr, c.n_over, c.mla, c.mlb, c.mlc, kp, d.scores + mr,
+                            d.final7 + (size_t)NSTATE * mr, d.ws, c.ws, s, d.tb, d.tboff + mr);
+  if (rc) return rc;
+  // the strip and grid triples are walked segment by segment below; every other one has its whole cube
+  const int32_t mw = c.strip || c.grid ? mr : m;
+  if (mw)
+    hipLaunchKernelGGL(tb_walk_batch, dim3((mw + 63) / 64), dim3(64), 0, s, d.tb, d.tboff, d.off, mw, d.final7,
+                       d.moves, d.info);
+  if (c.strip) {
+    // forward: the y faces of every strip but the last; then the strips, last
+    // to first, each followed by the walk of its pointers. j < 0: the forward form.
+    for (int32_t j = c.max_nty >= 2 ? -1 : 0; j < c.max_nty; ++j) {
+      if ((rc = align_launch_strip(d.seqs, d.off + 3 * (size_t)mr, c.n_over, pl.tymax, pl.tzmax, c.tile_pos,
+                                   c.tile_lds, kp, j, d.walk, d.scores + mr, d.final7 + (size_t)NSTATE * mr, d.tb,
+                                   d.tboff + mr, d.faces, d.faceoff + mr, s)))
+        return rc;
+      if (j >= 0)
+        hipLaunchKernelGGL(tb_walk_strip, dim3((c.n_over + 63) / 64), dim3(64), 0, s, d.tb, d.tboff + mr,
+                           d.off + 3 * (size_t)mr, c.n_over, pl.tymax, pl.tzmax, j, d.final7 + (size_t)NSTATE * mr,
+                           d.walk, d.moves, d.info + 4 * (size_t)mr);
+    }
+  }
+  if (c.grid) {
+    // forward: diagonal by diagonal, every tile but the last of each triple;
+    // then the tile each walker stands in, followed by the walk of its pointers,
+    // as often as the longest path can change tiles
+    for (int32_t j = 0; j < 2 * c.max_diag - 1; ++j) {
+      const bool fwd = j < c.max_diag - 1;
+      const int32_t dg = fwd ? j : j - (c.max_diag - 1);
+      if ((rc = align_launch_grid(d.seqs, d.off + 3 * (size_t)mr, c.n_over, pl.tymax, pl.tzmax, c.tile_pos,
+                                  c.tile_lds, kp, fwd, dg, c.max_len, d.walk, d.scores + mr,
+                                  d.final7 + (size_t)NSTATE * mr, d.tb, d.tboff + mr, d.faces, d.faceoff + mr, s)))
+        return rc;
+      if (!fwd)
+        hipLaunchKernelGGL(tb_walk_grid, dim3((c.n_over + 63) / 64), dim3(64), 0, s, d.tb, d.tboff + mr,
+                           d.off + 3 * (size_t)mr, c.n_over, pl.tymax, pl.tzmax, dg, d.final7 + (size_t)NSTATE * mr,
+                           d.walk, d.moves, d.info + 4 * (size_t)mr);
+    }
+  }
+  return TSA_OK;
+}
+
+// The traceback of n validated triples on the current device: plan pl, chunks
+// of at most `budget` bytes of pointer cubes. Outputs as tsa_align_batch's.
+int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KParams &kp, const AlignPlan &pl,
+              size_t budget, int32_t *scores, uint8_t *moves, int32_t *n_moves, int32_t *starts) {
+  const std::vector<AlignTriple> T = align_plan_triples(offsets, n, pl, false);
+  std::vector<AlignChunk> chunks;
+  int rc = align_plan_chunks(T, pl, budget, &chunks);
+  if (rc) return rc;
+  size_t max_cube = 0, max_seq = 0, max_ws = 0, max_face = 0;
+  int32_t max_n = 0;
+  for (const AlignChunk &c : chunks) {
     max_cube = std::max(max_cube, c.cube), max_seq = std::max(max_seq, c.seq);
     max_ws = std::max(max_ws, c.ws), max_face = std::max(max_face, c.face);
-    max_n = std::max(max_n, j - i);
-    i = j;
+    max_n = std::max(max_n, c.i1 - c.i0);
   }
   // device buffers, once per call, sized for the largest chunk
   AlignBufs B;
@@ -234,9 +304,7 @@ int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KPar
   std::vector<int64_t> h_meta(5 * (size_t)max_n + 1);
   std::vector<int32_t> h_res(12 * (size_t)max_n), order((size_t)max_n);
   for (const AlignChunk &c : chunks) {
-    // resident triples first, then the over-capacity ones (tiled, plane, strip or
-    // grid, one path for all of a chunk), packed back to back, so each path sees a
-    // contiguous sub-batch
+    // launch order: resident triples first, then the over-capacity ones
     const int32_t m = c.i1 - c.i0, mr = m - c.n_over;
     int32_t r = 0, v = mr;
     for (int32_t i = c.i0; i < c.i1; ++i) order[T[i].over ? v++ : r++] = i;
@@ -253,60 +321,15 @@ int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KPar
       if (c.tiled || c.strip || c.grid) cells += (int64_t)t.face;
     }
     h_off[3 * m] = pos;
-    int32_t *d_scores = d_res, *d_final7 = d_res + m, *d_info = d_res + 8 * (size_t)m;
-    const int64_t *d_off = d_meta, *d_tboff = d_meta + 3 * (size_t)m + 1, *d_faceoff = d_tboff + m;
+    AlignDev d;
+    d.seqs = d_seqs, d.off = d_meta, d.tboff = d_meta + 3 * (size_t)m + 1, d.faceoff = d.tboff + m;
+    d.scores = d_res, d.final7 = d_res + m, d.info = d_res + 8 * (size_t)m;
+    d.moves = d_moves, d.tb = d_tb, d.faces = d_faces, d.ws = d_ws, d.walk = d_walk;
     if (hipMemcpyAsync(d_seqs, h_seqs.data(), (size_t)pos, hipMemcpyHostToDevice, B.s) != hipSuccess ||
         hipMemcpyAsync(d_meta, h_meta.data(), sizeof(int64_t) * (5 * (size_t)m + 1), hipMemcpyHostToDevice, B.s) !=
             hipSuccess)
       return TSA_EDEVICE;
-    int rc = TSA_OK;
-    if (mr && (rc = align_launch_resident(d_seqs, d_off, mr, c.max_pos, c.lds, kp, d_scores, d_final7, d_tb, d_tboff,
-                                          B.s)))
-      return rc;
-    if (c.tiled)
-      rc = align_launch_tiled(d_seqs, d_off + 3 * (size_t)mr, c.n_over, pl.tymax, pl.tzmax, c.tile_pos, c.tile_lds, kp,
-                              d_scores + mr, d_final7 + (size_t)NSTATE * mr, d_tb, d_tboff + mr, d_faces,
-                              d_faceoff + mr, B.s);
-    else if (c.n_over && !c.strip && !c.grid)
-      rc = plane_launch_batch(d_seqs, d_off + 3 * (size_t)mr, c.n_over, c.mla, c.mlb, c.mlc, kp, d_scores + mr,
-                              d_final7 + (size_t)NSTATE * mr, d_ws, c.ws, B.s, d_tb, d_tboff + mr);
-    if (rc) return rc;
-    // the strip and grid triples are walked segment by segment below; every other one has its whole cube
-    const int32_t mw = c.strip || c.grid ? mr : m;
-    if (mw)
-      hipLaunchKernelGGL(tb_walk_batch, dim3((mw + 63) / 64), dim3(64), 0, B.s, d_tb, d_tboff, d_off, mw, d_final7,
-                         d_moves, d_info);
-    if (c.strip) {
-      // forward: the y faces of every strip but the last; then the strips, last
-      // to first, each followed by the walk of its pointers. j < 0: the forward form.
-      for (int32_t j = c.max_nty >= 2 ? -1 : 0; j < c.max_nty; ++j) {
-        if ((rc = align_launch_strip(d_seqs, d_off + 3 * (size_t)mr, c.n_over, pl.tymax, pl.tzmax, c.tile_pos,
-                                     c.tile_lds, kp, j, d_walk, d_scores + mr, d_final7 + (size_t)NSTATE * mr, d_tb,
-                                     d_tboff + mr, d_faces, d_faceoff + mr, B.s)))
-          return rc;
-        if (j >= 0)
-          hipLaunchKernelGGL(tb_walk_strip, dim3((c.n_over + 63) / 64), dim3(64), 0, B.s, d_tb, d_tboff + mr,
-                             d_off + 3 * (size_t)mr, c.n_over, pl.tymax, pl.tzmax, j, d_final7 + (size_t)NSTATE * mr,
-                             d_walk, d_moves, d_info + 4 * (size_t)mr);
-      }
-    }
-    if (c.grid) {
-      // forward: diagonal by diagonal, every tile but the last of each triple;
-      // then the tile each walker stands in, followed by the walk of its pointers,
-      // as often as the longest path can change tiles
-      for (int32_t j = 0; j < 2 * c.max_diag - 1; ++j) {
-        const bool fwd = j < c.max_diag - 1;
-        const int32_t d = fwd ? j : j - (c.max_diag - 1);
-        if ((rc = align_launch_grid(d_seqs, d_off + 3 * (size_t)mr, c.n_over, pl.tymax, pl.tzmax, c.tile_pos,
-                                    c.tile_lds, kp, fwd, d, c.max_len, d_walk, d_scores + mr,
-                                    d_final7 + (size_t)NSTATE * mr, d_tb, d_tboff + mr, d_faces, d_faceoff + mr, B.s)))
-          return rc;
-        if (!fwd)
-          hipLaunchKernelGGL(tb_walk_grid, dim3((c.n_over + 63) / 64), dim3(64), 0, B.s, d_tb, d_tboff + mr,
-                             d_off + 3 * (size_t)mr, c.n_over, pl.tymax, pl.tzmax, d, d_final7 + (size_t)NSTATE * mr,
-                             d_walk, d_moves, d_info + 4 * (size_t)mr);
-      }
-    }
+    if ((rc = align_queue_chunk(c, pl, kp, d, B.s))) return rc;
     if (hipGetLastError() != hipSuccess ||
         hipMemcpyAsync(h_res.data(), d_res, sizeof(int32_t) * 12 * (size_t)m, hipMemcpyDeviceToHost, B.s) !=
             hipSuccess ||
@@ -324,6 +347,71 @@ int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KPar
       starts[3 * (int64_t)i] = info[1], starts[3 * (int64_t)i + 1] = info[2], starts[3 * (int64_t)i + 2] = info[3];
     }
   }
+  return TSA_OK;
+}
+
+// ---- tsa_align_batch_async: the same plan against a caller's workspace -----
+constexpr size_t kAlign256 = 256;
+inline size_t up256(size_t v) { return (v + kAlign256 - 1) & ~(kAlign256 - 1); }
+
+// The fixed part of the workspace, sized for the whole call from n, the total
+// of symbols L and whether the path keeps walker records: byte offsets of its
+// regions, each 256-byte aligned, and `total`, where the faces and cubes of a
+// chunk begin. Chunk [i0, i1) uses entries i0.. of every per-triple region and
+// the bytes of its triples in seqs and moves; its 3m+1 packed offsets start at
+// entry 3*i0 + (index of the chunk), so off holds 3n + (chunks <= n) entries.
+struct AlignFixed {
+  size_t seqs, moves, off, tboff, faceoff, order, scores, final7, info, walk, total;
+};
+AlignFixed align_fixed_layout(int32_t n, size_t L, bool walk) {
+  AlignFixed f;
+  size_t at = 0;
+  const auto take = [&](size_t bytes) {
+    const size_t here = at;
+    at += up256(bytes);
+    return here;
+  };
+  f.seqs = take(L), f.moves = take(L);
+  f.off = take(sizeof(int64_t) * 4 * (size_t)n);
+  f.tboff = take(sizeof(int64_t) * (size_t)n), f.faceoff = take(sizeof(int64_t) * (size_t)n);
+  f.order = take(sizeof(int32_t) * (size_t)n), f.scores = take(sizeof(int32_t) * (size_t)n);
+  f.final7 = take(sizeof(int32_t) * NSTATE * (size_t)n), f.info = take(sizeof(int32_t) * 4 * (size_t)n);
+  f.walk = take(walk ? sizeof(int32_t) * ALIGN_WALK_REC * (size_t)n : 0);
+  f.total = at;
+  return f;
+}
+
+// What tsa_align_workspace_size prices and tsa_align_batch_async runs: the
+// validated plan of a batch. cap: the budget of a chunk at most (align_tb_bytes).
+struct AlignAsyncPlan {
+  AlignPlan pl;
+  std::vector<AlignTriple> T;
+  AlignFixed fixed;
+  size_t max_need = 0, cap = SIZE_MAX;
+};
+int align_async_plan(const int64_t *h_offsets, int32_t n, const tsa_params *p, int32_t path, AlignAsyncPlan *A) {
+  if (!h_offsets || n < 0 || !params_ok(p)) return TSA_EINVAL;
+  if (path != TSA_ALIGN_PATH_TILED && path != TSA_ALIGN_PATH_STRIP && path != TSA_ALIGN_PATH_GRID) return TSA_EINVAL;
+  for (int32_t i = 0; i < n; ++i) {
+    const int64_t *o = h_offsets + 3 * (int64_t)i;
+    if (o[1] <= o[0] || o[2] <= o[1] || o[3] <= o[2] || o[3] - o[0] > INT32_MAX) return TSA_EINVAL;
+  }
+  int rc = align_plan_read(&A->pl);
+  if (rc) return rc;
+  if (!A->pl.mode_set)
+    A->pl.mode = path == TSA_ALIGN_PATH_STRIP ? ALIGN_MODE_STRIP : path == TSA_ALIGN_PATH_GRID ? ALIGN_MODE_GRID
+                                                                                               : ALIGN_MODE_TILED;
+  else if (A->pl.mode != ALIGN_MODE_TILED && A->pl.mode != ALIGN_MODE_STRIP && A->pl.mode != ALIGN_MODE_GRID)
+    return TSA_EINVAL;  // no resident-or-plane plan and no plane sweep on this path
+  long ov = 0;
+  if (override_int("align_tb_bytes", &ov)) {
+    if (ov < 0) return TSA_EINVAL;
+    A->cap = (size_t)ov;
+  }
+  A->T = align_plan_triples(h_offsets, n, A->pl, true);
+  for (const AlignTriple &t : A->T) A->max_need = std::max(A->max_need, t.need);
+  A->fixed = align_fixed_layout(n, n ? (size_t)(h_offsets[3 * (int64_t)n] - h_offsets[0]) : 0,
+                                A->pl.mode == ALIGN_MODE_STRIP || A->pl.mode == ALIGN_MODE_GRID);
   return TSA_OK;
 }
 }  // namespace
@@ -428,6 +516,77 @@ int tsa_align_batch_lowmem(const uint8_t *seqs, const int64_t *offsets, int32_t 
 int tsa_align_batch_grid(const uint8_t *seqs, const int64_t *offsets, int32_t n, const tsa_params *p,
                          int32_t *scores, uint8_t *moves, int32_t *n_moves, int32_t *starts, int32_t device) {
   return align_batch_entry(seqs, offsets, n, p, scores, moves, n_moves, starts, device, ALIGN_MODE_GRID);
+}
+
+int tsa_align_workspace_size(const int64_t *h_offsets, int32_t n, const tsa_params *p, int32_t path,
+                             size_t *min_bytes, size_t *full_bytes) {
+  if (!min_bytes || !full_bytes) return TSA_EINVAL;
+  AlignAsyncPlan A;
+  int rc = align_async_plan(h_offsets, n, p, path, &A);
+  if (rc) return rc;
+  *min_bytes = *full_bytes = 0;
+  if (n == 0) return TSA_OK;
+  // the fewest chunks: the budget bounds none (but align_tb_bytes), only the 65535 triples of a chunk do
+  std::vector<AlignChunk> chunks;
+  if ((rc = align_plan_chunks(A.T, A.pl, A.cap, &chunks))) return rc;
+  size_t most = 0;
+  for (const AlignChunk &c : chunks) most = std::max(most, c.need);
+  *min_bytes = A.fixed.total + A.max_need;
+  *full_bytes = A.fixed.total + most;
+  return TSA_OK;
+}
+
+int tsa_align_batch_async(const uint8_t *d_seqs, const int64_t *d_offsets, const int64_t *h_offsets, int32_t n,
+                          const tsa_params *p, int32_t path, int32_t *d_scores, uint8_t *d_moves, int32_t *d_n_moves,
+                          int32_t *d_starts, void *d_workspace, size_t workspace_bytes, void *stream) {
+  if (!d_seqs || !d_offsets || !d_scores || !d_moves || !d_n_moves || !d_starts || !d_workspace) return TSA_EINVAL;
+  if ((uintptr_t)d_workspace % kAlign256) return TSA_EINVAL;
+  AlignAsyncPlan A;
+  int rc = align_async_plan(h_offsets, n, p, path, &A);
+  if (rc) return rc;
+  if (n == 0) return TSA_OK;
+  if (tsa_device_count() <= 0) return TSA_ENODEV;
+  KParams kp;
+  if ((rc = build_kparams(p, &kp))) return rc;
+  if (workspace_bytes < A.fixed.total || workspace_bytes - A.fixed.total < A.max_need) return TSA_ENOMEM;
+  std::vector<AlignChunk> chunks;
+  if ((rc = align_plan_chunks(A.T, A.pl, std::min(workspace_bytes - A.fixed.total, A.cap), &chunks))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  uint8_t *w = (uint8_t *)d_workspace;
+  const AlignFixed &f = A.fixed;
+  (void)hipGetLastError();  // an error left over from an earlier call is not this call's
+  for (size_t k = 0; k < chunks.size(); ++k) {
+    const AlignChunk &c = chunks[k];
+    const int32_t m = c.i1 - c.i0;
+    const size_t sym0 = (size_t)(h_offsets[3 * (int64_t)c.i0] - h_offsets[0]);  // the chunk's place in seqs and moves
+    AlignChunkBufs b;
+    b.off = (int64_t *)(w + f.off) + 3 * (size_t)c.i0 + k;
+    b.tb_off = (int64_t *)(w + f.tboff) + c.i0, b.face_off = (int64_t *)(w + f.faceoff) + c.i0;
+    b.order = (int32_t *)(w + f.order) + c.i0, b.scores = (int32_t *)(w + f.scores) + c.i0;
+    b.final7 = (int32_t *)(w + f.final7) + (size_t)NSTATE * c.i0, b.info = (int32_t *)(w + f.info) + 4 * (size_t)c.i0;
+    b.seqs = w + f.seqs + sym0, b.moves = w + f.moves + sym0;
+    AlignDev d;
+    d.seqs = b.seqs, d.off = b.off, d.tboff = b.tb_off, d.faceoff = b.face_off;
+    d.scores = b.scores, d.final7 = b.final7, d.info = b.info, d.moves = b.moves;
+    // the faces (16-byte cells) first, then the cubes (words): c.face + c.cube = c.need bytes
+    d.faces = w + f.total, d.tb = (uint32_t *)(w + f.total + c.face), d.ws = nullptr;
+    d.walk = (int32_t *)(w + f.walk) + (size_t)ALIGN_WALK_REC * c.i0;
+    align_launch_meta(d_offsets, c.i0, m, A.pl, b, s);
+    align_launch_pack(d_seqs, d_offsets, m, b, s);
+    if ((rc = align_queue_chunk(c, A.pl, kp, d, s))) return rc;
+    align_launch_finish(d_offsets, m, b, d_scores, d_moves, d_n_moves, d_starts, s);
+  }
+  return hipGetLastError() == hipSuccess ? TSA_OK : TSA_EDEVICE;
+}
+
+int tsa_align_rows_async(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, const uint8_t *d_moves,
+                         const int32_t *d_n_moves, const int32_t *d_starts, uint8_t *d_rows, void *stream) {
+  if (!d_seqs || !d_offsets || !d_moves || !d_n_moves || !d_starts || !d_rows || n < 0) return TSA_EINVAL;
+  if (n == 0) return TSA_OK;
+  if (tsa_device_count() <= 0) return TSA_ENODEV;
+  (void)hipGetLastError();
+  align_launch_rows(d_seqs, d_offsets, n, d_moves, d_n_moves, d_starts, d_rows, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? TSA_OK : TSA_EDEVICE;
 }
 
 // One triple, always by the plane sweep, with buffers and a one-thread walk of

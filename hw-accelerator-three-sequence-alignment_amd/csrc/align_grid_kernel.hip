@@ -52,16 +52,6 @@ namespace tsa {
 
 constexpr int GRID_NT = 1024;  // as the tiled kernel's: align_tile_fits bounds a tile to 3 positions per thread
 
-size_t align_grid_cube_bytes(int32_t la, int32_t lb, int32_t lc, int32_t tymax, int32_t tzmax) {
-  const AlignTileGeom g = align_tile_geom(lb, lc, tymax, tzmax);
-  return sizeof(uint32_t) * (size_t)g.TY * (size_t)(la + g.TZ - 1) * (size_t)g.TZ;
-}
-
-size_t align_grid_face_cells(int32_t la, int32_t lb, int32_t lc, int32_t tymax, int32_t tzmax) {
-  const AlignTileGeom g = align_tile_geom(lb, lc, tymax, tzmax);
-  return (size_t)(g.nty - 1) * (size_t)la * ((size_t)lc + 1) + (size_t)(g.ntz - 1) * (size_t)la * (size_t)lb;
-}
-
 // FWD: launch d of the forward form (walk is not read). Otherwise launch d of
 // the backward form; walk = the walker records of tb_walk_grid, ALIGN_WALK_REC
 // words a triple.

@@ -2,7 +2,10 @@
 // resident kernel (align_kernel.hip), the tiled resident kernel
 // (align_tiled_kernel.hip), the strip kernel (align_strip_kernel.hip), the grid
 // kernels (align_grid_kernel.hip), the batch form of the TB plane sweep and the
-// batched walks (plane_kernel.hip).
+// batched walks (plane_kernel.hip); and the helper kernels of the device-resident
+// entry points (align_async_kernel.hip). The sizing functions and the plan of a
+// triple are __host__ __device__: the host planner and the kernel that builds a
+// chunk's metadata on the device read one definition.
 #pragma once
 
 #include "tsa_internal.h"
@@ -31,9 +34,29 @@ __global__ void tb_walk_batch(const uint32_t *tb, const int64_t *tb_off, const i
 // The resident traceback kernel: one workgroup sweeps a whole cube in one
 // launch, its (y,z) planes in LDS. fits: lb*lc positions within the
 // workgroup's registers and both planes within LDS (la is not bounded).
-bool align_resident_fits(int32_t la, int32_t lb, int32_t lc);
+// ALIGN_RESIDENT_POS = its 1024 threads x 4 positions, ALIGN_LDS_BYTES = the
+// 160 KiB of LDS (pencil_common.h's LDS_MAX); align_kernel.hip asserts both.
+constexpr int64_t ALIGN_RESIDENT_POS = 4096;
+constexpr size_t ALIGN_LDS_BYTES = 160 * 1024;
+__host__ __device__ inline size_t align_cells_bytes(int32_t lb, int32_t lc) {
+  return 2 * sizeof(uint4) * (size_t)(lb + 1) * (size_t)(lc + 1);
+}
+__host__ __device__ inline bool align_resident_fits(int32_t la, int32_t lb, int32_t lc) {
+  (void)la;  // A is staged when it fits and read from global memory when not
+  return (int64_t)lb * lc <= ALIGN_RESIDENT_POS && align_cells_bytes(lb, lc) + lb + lc <= ALIGN_LDS_BYTES;
+}
 // Dynamic LDS a (la,lb,lc) triple asks for (A staged when there is room).
-size_t align_resident_lds(int32_t la, int32_t lb, int32_t lc);
+__host__ __device__ inline size_t align_resident_lds(int32_t la, int32_t lb, int32_t lc) {
+  size_t need = align_cells_bytes(lb, lc) + (size_t)lb + lc;
+  if (need + (size_t)la <= ALIGN_LDS_BYTES) need += la;
+  need = (need + 15) & ~(size_t)15;
+  return need < ALIGN_LDS_BYTES ? need : ALIGN_LDS_BYTES;
+}
+// Bytes of the pointer cube of one (la,lb,lc) triple: tsa_internal.h's
+// tb_cube_bytes (plane_kernel.hip, host only) returns this.
+__host__ __device__ inline size_t align_cube_bytes(int32_t la, int32_t lb, int32_t lc) {
+  return (size_t)lb * (size_t)(la + lc - 1) * (size_t)lc * sizeof(uint32_t);
+}
 // One launch for n triples that all fit, through launch_with_lds (so
 // tsa_kernel_launch_count counts it): max_pos = the largest lb*lc and lds =
 // the largest align_resident_lds of the batch.
@@ -66,7 +89,11 @@ bool align_tile_fits(int32_t ty, int32_t tz);
 constexpr int32_t ALIGN_TILE_Y = 64, ALIGN_TILE_Z = 48;
 // 16-byte cells of a triple's face workspace: two y faces [la][lc+1] and two
 // z faces [la][TY].
-size_t align_tiled_face_cells(int32_t la, int32_t lb, int32_t lc, int32_t tymax, int32_t tzmax);
+__host__ __device__ inline size_t align_tiled_face_cells(int32_t la, int32_t lb, int32_t lc, int32_t tymax,
+                                                         int32_t tzmax) {
+  const AlignTileGeom g = align_tile_geom(lb, lc, tymax, tzmax);
+  return 2 * (size_t)la * ((size_t)lc + 1) + 2 * (size_t)la * (size_t)g.TY;
+}
 // One launch for n triples through launch_with_lds: max_pos = the largest
 // TY*TZ and lds = the largest align_resident_lds(la, TY, TZ) of the batch;
 // d_face_off[t] = the cell offset of triple t's face workspace in d_faces.
@@ -81,10 +108,18 @@ int align_launch_tiled(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t 
 // nty-1-j of every triple again, with pointers, into a cube of one strip, and
 // tb_walk_strip follows them before launch j+1 overwrites it.
 // Bytes of a triple's strip cube, TY*(la+lc-1)*lc words.
-size_t align_strip_cube_bytes(int32_t la, int32_t lb, int32_t lc, int32_t tymax, int32_t tzmax);
+__host__ __device__ inline size_t align_strip_cube_bytes(int32_t la, int32_t lb, int32_t lc, int32_t tymax,
+                                                         int32_t tzmax) {
+  const AlignTileGeom g = align_tile_geom(lb, lc, tymax, tzmax);
+  return sizeof(uint32_t) * (size_t)g.TY * (size_t)(la + lc - 1) * (size_t)lc;
+}
 // 16-byte cells of its face workspace: nty-1 kept y faces [la][lc+1] and two
 // z faces [la][TY].
-size_t align_strip_face_cells(int32_t la, int32_t lb, int32_t lc, int32_t tymax, int32_t tzmax);
+__host__ __device__ inline size_t align_strip_face_cells(int32_t la, int32_t lb, int32_t lc, int32_t tymax,
+                                                         int32_t tzmax) {
+  const AlignTileGeom g = align_tile_geom(lb, lc, tymax, tzmax);
+  return (size_t)(g.nty - 1) * (size_t)la * ((size_t)lc + 1) + 2 * (size_t)la * (size_t)g.TY;
+}
 // The walker record of a triple, int32 words {x, y, z, T, n, done}: where the
 // walk stands, the state it is in, the moves it has made and whether the path
 // has reached a zero face.
@@ -117,11 +152,19 @@ __global__ void tb_walk_strip(const uint32_t *tb, const int64_t *tb_off, const i
 // walker stands in, up to the walker's x, and tb_walk_grid follows them before
 // launch j+1 overwrites it.
 // Bytes of a triple's tile cube, TY*(la+TZ-1)*TZ words.
-size_t align_grid_cube_bytes(int32_t la, int32_t lb, int32_t lc, int32_t tymax, int32_t tzmax);
+__host__ __device__ inline size_t align_grid_cube_bytes(int32_t la, int32_t lb, int32_t lc, int32_t tymax,
+                                                        int32_t tzmax) {
+  const AlignTileGeom g = align_tile_geom(lb, lc, tymax, tzmax);
+  return sizeof(uint32_t) * (size_t)g.TY * (size_t)(la + g.TZ - 1) * (size_t)g.TZ;
+}
 // 16-byte cells of its kept faces: nty-1 y faces [la][lc+1] and ntz-1 z faces
 // [la][lb]. A grid triple's need against the budget is the sum of both:
 //   4*TY*(la+TZ-1)*TZ + 16*((nty-1)*la*(lc+1) + (ntz-1)*la*lb)  bytes.
-size_t align_grid_face_cells(int32_t la, int32_t lb, int32_t lc, int32_t tymax, int32_t tzmax);
+__host__ __device__ inline size_t align_grid_face_cells(int32_t la, int32_t lb, int32_t lc, int32_t tymax,
+                                                        int32_t tzmax) {
+  const AlignTileGeom g = align_tile_geom(lb, lc, tymax, tzmax);
+  return (size_t)(g.nty - 1) * (size_t)la * ((size_t)lc + 1) + (size_t)(g.ntz - 1) * (size_t)la * (size_t)lb;
+}
 // One launch through launch_with_lds. fwd: launch d of the forward form over
 // (n triples) x (ndiag indices along the diagonal, the most tiles any triple
 // has on one); a workgroup without a tile on diagonal d, or with the last tile,
@@ -143,5 +186,85 @@ int align_launch_grid(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n
 __global__ void tb_walk_grid(const uint32_t *tb, const int64_t *tb_off, const int64_t *offs, int32_t n,
                              int32_t tymax, int32_t tzmax, int32_t j, const int32_t *final7, int32_t *walk,
                              uint8_t *moves, int32_t *info);
+
+// ---- the plan of a triple (align_api.hip plans with it on the host,
+// align_meta_kernel on the device) ------------------------------------------
+// The plan mode: the override align_mode, or what the entry point plans when
+// it is not set (auto, strip under tsa_align_batch_lowmem, grid under
+// tsa_align_batch_grid, the path argument of tsa_align_batch_async).
+enum AlignMode {
+  ALIGN_MODE_AUTO, ALIGN_MODE_RESIDENT, ALIGN_MODE_PLANE, ALIGN_MODE_TILED, ALIGN_MODE_STRIP, ALIGN_MODE_GRID
+};
+// Passed to the meta kernel by value.
+struct AlignPlan {
+  int32_t mode = ALIGN_MODE_AUTO;
+  int32_t mode_set = 0;  // align_mode is set
+  int32_t capped = 0;    // align_tile is set
+  int32_t tymax = ALIGN_TILE_Y, tzmax = ALIGN_TILE_Z;
+};
+// Over capacity: the triple does not go to the resident kernel as a whole.
+// With align_tile set under align_mode = tiled, strip or grid that is any triple
+// larger than the tile (tests put tiny cubes through many tiles that way).
+__host__ __device__ inline bool align_over(const AlignPlan &pl, int32_t la, int32_t lb, int32_t lc) {
+  if ((pl.mode == ALIGN_MODE_TILED || pl.mode == ALIGN_MODE_STRIP || pl.mode == ALIGN_MODE_GRID) && pl.capped)
+    return lb > pl.tymax || lc > pl.tzmax;
+  return !align_resident_fits(la, lb, lc);
+}
+// What a triple asks of the device buffers: whether it is over capacity (under
+// align_mode = plane every triple is), the bytes of its pointer cube -- of its
+// strip cube on the strip path, its tile cube on the grid path -- and the
+// 16-byte cells of its face workspace if it is tiled, strips or grid.
+struct AlignNeed {
+  bool over;
+  size_t cube, face;
+};
+__host__ __device__ inline AlignNeed align_need(const AlignPlan &pl, int32_t la, int32_t lb, int32_t lc) {
+  AlignNeed t;
+  t.over = pl.mode == ALIGN_MODE_PLANE || align_over(pl, la, lb, lc);
+  const bool strip = t.over && pl.mode == ALIGN_MODE_STRIP, grid = t.over && pl.mode == ALIGN_MODE_GRID;
+  t.cube = strip  ? align_strip_cube_bytes(la, lb, lc, pl.tymax, pl.tzmax)
+           : grid ? align_grid_cube_bytes(la, lb, lc, pl.tymax, pl.tzmax)
+                  : align_cube_bytes(la, lb, lc);
+  t.face = strip    ? align_strip_face_cells(la, lb, lc, pl.tymax, pl.tzmax)
+           : grid   ? align_grid_face_cells(la, lb, lc, pl.tymax, pl.tzmax)
+           : t.over ? align_tiled_face_cells(la, lb, lc, pl.tymax, pl.tzmax)
+                    : 0;
+  return t;
+}
+
+// ---- the helper kernels of tsa_align_batch_async and tsa_align_rows_async
+// (align_async_kernel.hip). None is counted by tsa_kernel_launch_count. ------
+// The buffers of one chunk of m triples, caller's triples [i0, i0 + m), in
+// launch order: the resident triples first, then the over-capacity ones, each
+// group in the caller's order. What align_run builds on the host for the
+// synchronous entry points, align_launch_meta builds on the device.
+struct AlignChunkBufs {
+  int64_t *off;       // 3m+1 offsets of the packed sequences, from 0
+  int64_t *tb_off;    // m word offsets of the cubes, an exclusive scan
+  int64_t *face_off;  // m cell offsets of the face workspaces, an exclusive scan
+  int32_t *order;     // m: the caller's index of launch slot j
+  int32_t *scores;    // m
+  int32_t *final7;    // 7m
+  int32_t *info;      // 4m {moves, x0, y0, z0}, zeroed by the meta kernel
+  uint8_t *seqs;      // the packed sequences
+  uint8_t *moves;     // the moves, laid out as seqs
+};
+// One workgroup: reads d_offsets[3*i0 .. 3*(i0+m)] and fills off, tb_off,
+// face_off and order of the chunk under plan pl (align_need of every triple),
+// and zeroes info.
+void align_launch_meta(const int64_t *d_offsets, int32_t i0, int32_t m, const AlignPlan &pl, const AlignChunkBufs &b,
+                       hipStream_t stream);
+// One workgroup per triple: copies its la+lb+lc symbols from the caller's
+// d_seqs to its packed place b.seqs + b.off[3j].
+void align_launch_pack(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t m, const AlignChunkBufs &b,
+                       hipStream_t stream);
+// One workgroup per triple: score, n_moves (0 unless 1 <= moves <= la+lb+lc)
+// and start to the caller's index, and exactly n_moves bytes of moves to the
+// caller's slot d_moves + d_offsets[3i] - d_offsets[0].
+void align_launch_finish(const int64_t *d_offsets, int32_t m, const AlignChunkBufs &b, int32_t *d_scores,
+                         uint8_t *d_moves, int32_t *d_n_moves, int32_t *d_starts, hipStream_t stream);
+// The gapped rows of n alignments, one wave per triple (tsa_align_rows_async).
+void align_launch_rows(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, const uint8_t *d_moves,
+                       const int32_t *d_n_moves, const int32_t *d_starts, uint8_t *d_rows, hipStream_t stream);
 
 }  // namespace tsa

@@ -41,21 +41,8 @@ namespace tsa {
 
 constexpr int ALIGN_NT = 1024;  // threads of a workgroup at most
 constexpr int ALIGN_K = 4;      // positions per thread at most (115 VGPRs of the 128 a 1024-thread block has)
-
-static size_t align_cells_bytes(int32_t lb, int32_t lc) {
-  return 2 * sizeof(uint4) * (size_t)(lb + 1) * (size_t)(lc + 1);
-}
-
-bool align_resident_fits(int32_t la, int32_t lb, int32_t lc) {
-  (void)la;  // A is staged when it fits and read from global memory when not
-  return (int64_t)lb * lc <= (int64_t)ALIGN_NT * ALIGN_K && align_cells_bytes(lb, lc) + lb + lc <= LDS_MAX;
-}
-
-size_t align_resident_lds(int32_t la, int32_t lb, int32_t lc) {
-  size_t need = align_cells_bytes(lb, lc) + (size_t)lb + lc;
-  if (need + (size_t)la <= LDS_MAX) need += la;
-  return std::min<size_t>((need + 15) & ~(size_t)15, LDS_MAX);
-}
+static_assert((int64_t)ALIGN_NT * ALIGN_K == ALIGN_RESIDENT_POS && LDS_MAX == ALIGN_LDS_BYTES,
+              "align_kernel.h's capacity of the resident kernel");
 
 template <int K>
 __global__ __launch_bounds__(ALIGN_NT) void align_resident_kernel(

@@ -42,16 +42,6 @@ namespace tsa {
 
 constexpr int STRIP_NT = 1024;  // as the tiled kernel's: align_tile_fits bounds a tile to 3 positions per thread
 
-size_t align_strip_cube_bytes(int32_t la, int32_t lb, int32_t lc, int32_t tymax, int32_t tzmax) {
-  const AlignTileGeom g = align_tile_geom(lb, lc, tymax, tzmax);
-  return sizeof(uint32_t) * (size_t)g.TY * (size_t)(la + lc - 1) * (size_t)lc;
-}
-
-size_t align_strip_face_cells(int32_t la, int32_t lb, int32_t lc, int32_t tymax, int32_t tzmax) {
-  const AlignTileGeom g = align_tile_geom(lb, lc, tymax, tzmax);
-  return (size_t)(g.nty - 1) * (size_t)la * ((size_t)lc + 1) + 2 * (size_t)la * (size_t)g.TY;
-}
-
 // FWD: the forward form (j is not read). Otherwise launch j of the strip form;
 // walk = the walker records of tb_walk_strip, ALIGN_WALK_REC words a triple.
 template <int K, bool FWD>

@@ -50,11 +50,6 @@ bool align_tile_fits(int32_t ty, int32_t tz) {
   return ty >= 1 && tz >= 1 && (int64_t)ty * tz <= (int64_t)TILED_NT * TILED_K && align_resident_fits(1, ty, tz);
 }
 
-size_t align_tiled_face_cells(int32_t la, int32_t lb, int32_t lc, int32_t tymax, int32_t tzmax) {
-  const AlignTileGeom g = align_tile_geom(lb, lc, tymax, tzmax);
-  return 2 * (size_t)la * ((size_t)lc + 1) + 2 * (size_t)la * (size_t)g.TY;
-}
-
 template <int K>
 __global__ __launch_bounds__(TILED_NT) void align_tiled_kernel(
     const uint8_t *__restrict__ seqs, const int64_t *__restrict__ offs, KParams kp, uint32_t lds_bytes,

@@ -409,9 +409,7 @@ __global__ __launch_bounds__(64) void tb_walk_grid(const uint32_t *__restrict__ 
   }
 }
 
-size_t tb_cube_bytes(int32_t la, int32_t lb, int32_t lc) {
-  return (size_t)lb * (size_t)(la + lc - 1) * (size_t)lc * sizeof(uint32_t);
-}
+size_t tb_cube_bytes(int32_t la, int32_t lb, int32_t lc) { return align_cube_bytes(la, lb, lc); }
 
 int plane_launch_batch(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n,
                        int32_t max_la, int32_t max_lb, int32_t max_lc, const KParams &kp,

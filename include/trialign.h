@@ -316,6 +316,90 @@ int tsa_align_batch_grid(const uint8_t *seqs, const int64_t *offsets, int32_t n,
                          const tsa_params *p, int32_t *scores, uint8_t *moves,
                          int32_t *n_moves, int32_t *starts, int32_t device);
 
+/* Device-resident traceback: tsa_align_batch on sequences that are already in
+ * device memory, with results that stay there. d_* are device pointers on the
+ * current device, stream is a hipStream_t (NULL = default stream). h_offsets
+ * is a host copy of the same 3n+1 offsets: the call reads it for validation
+ * and planning and never after it returns; the device reads d_offsets. That the
+ * two agree is the caller's job, as is the validation of symbols (tsa_validate
+ * on the host copy), exactly as for tsa_score_batch_async.
+ * Outputs are laid out as tsa_align_batch's: triple i owns
+ *   d_moves[h_offsets[3i] - h_offsets[0] .. h_offsets[3i+3] - h_offsets[0]),
+ * whose first d_n_moves[i] bytes receive its columns in forward order; the
+ * bytes of the slot beyond them are not written. d_starts[3i..3i+2] and
+ * d_scores[i] as in tsa_align_batch. d_n_moves[i] == 0 is never a valid result:
+ * it flags a triple whose walk came out of range (what the synchronous entry
+ * points report as TSA_EINTERNAL). Results equal tsa_align_batch's for every
+ * triple and parameter set, move for move: literal wrapped arithmetic, lowest
+ * state index on ties, free start.
+ * The call only queues work: no device allocation, no copy to or from host
+ * memory, no query of free memory, no stream of its own and no
+ * synchronisation (the metadata of a chunk is built by a kernel from d_offsets,
+ * since a copy from pageable host memory would wait for the stream).
+ * Thread-safe; two calls in flight need two workspaces.
+ * Triples that fit one workgroup run the resident kernel with a whole cube;
+ * the others take `path`: TSA_ALIGN_PATH_TILED the tiled resident kernel,
+ * whatever their number (the plane sweep is not available here: it costs
+ * la+lb+lc launches per chunk and its workspace is not additive per triple;
+ * tsa_describe_align_plan under align_mode = tiled describes the plan),
+ * TSA_ALIGN_PATH_STRIP the strip path of tsa_align_batch_lowmem,
+ * TSA_ALIGN_PATH_GRID the grid path of tsa_align_batch_grid. Overrides:
+ * align_tile holds as everywhere; a set align_mode of tiled, strip or grid
+ * replaces `path` (a set override holds), align_mode = resident or plane makes
+ * tsa_align_workspace_size and tsa_align_batch_async return TSA_EINVAL;
+ * align_tb_bytes, when set, caps the budget of a chunk from above.
+ * The workspace (256-byte aligned) holds a fixed part sized for the whole call
+ * -- the packed sequences and moves, the metadata of the chunks, the results
+ * and the walker records of strip or grid triples, each region 256-byte
+ * aligned -- then the face buffers and the pointer cubes of one chunk. The
+ * budget of a chunk is workspace_bytes minus the fixed part, and a triple's
+ * need against it is: resident, the cube (4*lb*(la+lc-1)*lc bytes); tiled, the
+ * cube plus its face workspace (32*la*(lc+1) + 32*la*TY bytes); strip and grid,
+ * the needs stated at tsa_align_batch_lowmem and tsa_align_batch_grid. Chunks
+ * are consecutive triples whose needs fit the budget together, at most 65535,
+ * and a chunk queues the counted launches (tsa_kernel_launch_count) of the
+ * synchronous entry point of its path; the helper kernels that build the
+ * metadata, pack the sequences and scatter the results, and the walks, are not
+ * counted. tsa_align_workspace_size (host-only, no device needed, validation
+ * as below) prices that plan: min_bytes = the fixed part + the largest need of
+ * a triple, the smallest workspace the call succeeds with; full_bytes = the
+ * size from which the batch takes the fewest chunks possible. Any size in
+ * between works, with more chunks.
+ * Validation comes before any device work: TSA_EINVAL for null pointers,
+ * n < 0, non-monotone h_offsets or a length below 1, bad parameters, an unknown
+ * path, an override value that is not valid or a workspace that is not
+ * 256-byte aligned; TSA_OK for n == 0; TSA_ENODEV with no HIP device;
+ * TSA_ENOMEM when workspace_bytes < min_bytes, with nothing queued. No RTL
+ * counterpart (see tsa_align_gpu). */
+#define TSA_ALIGN_PATH_TILED 0 /* larger triples: tiled resident kernel, whole cube */
+#define TSA_ALIGN_PATH_STRIP 1 /* ... the strip path of tsa_align_batch_lowmem       */
+#define TSA_ALIGN_PATH_GRID 2  /* ... the grid path of tsa_align_batch_grid          */
+int tsa_align_workspace_size(const int64_t *h_offsets, int32_t n, const tsa_params *p,
+                             int32_t path, size_t *min_bytes, size_t *full_bytes);
+int tsa_align_batch_async(const uint8_t *d_seqs, const int64_t *d_offsets,
+                          const int64_t *h_offsets, int32_t n, const tsa_params *p,
+                          int32_t path, int32_t *d_scores, uint8_t *d_moves,
+                          int32_t *d_n_moves, int32_t *d_starts,
+                          void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* The three gapped rows of n alignments, on the device (queues one launch on
+ * stream, no synchronisation, no workspace). d_seqs and d_offsets as above;
+ * d_moves, d_n_moves and d_starts in tsa_align_batch's layout, from
+ * tsa_align_batch_async or uploaded from any of the synchronous entry points.
+ * d_rows has three times the layout of d_moves: triple i, of len_i = la+lb+lc
+ * symbols, owns 3*len_i bytes at d_rows + 3*(offsets[3i] - offsets[0]), row r
+ * (0 = A, 1 = B, 2 = C) at + r*len_i. The first d_n_moves[i] bytes of each row
+ * receive one code per alignment column, "ATCGN-"[code]: the symbol the column
+ * consumes from that sequence (0..4 as stored, N stays 4) or TSA_ROW_GAP. The
+ * bytes beyond them are not written, and nothing is when d_n_moves[i] is 0.
+ * Moves that do not belong to these sequences give unspecified rows but no
+ * access outside the buffers. TSA_EINVAL for a null pointer or n < 0, TSA_OK
+ * for n == 0, TSA_ENODEV with no HIP device. */
+#define TSA_ROW_GAP 5
+int tsa_align_rows_async(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n,
+                         const uint8_t *d_moves, const int32_t *d_n_moves,
+                         const int32_t *d_starts, uint8_t *d_rows, void *stream);
+
 /* Which path tsa_align_batch takes for a group (one chunk) of n triples of
  * these lengths under the current overrides, as a short text that begins with
  * "resident", "tiled", "strip", "grid" or "plane"; for tiled it carries the tile and

@@ -15,6 +15,15 @@ synchronous, so host wall time is the time a caller waits.
 tiled, strip or grid; --tb-bytes sets align_tb_bytes for every batch form, and a form
 the library refuses, such as tiled with a cube over that budget, is recorded
 with its error instead of a time).
+--async adds, for every batch form but plane, a leg through tsa_align_batch_async
+(<form>_async_ms): the same batch with its sequences and offsets already on
+the device and a full_bytes workspace, timed with one event pair around a train
+of --train calls on one stream and divided by the train, next to the
+synchronous leg in the same process; its results stay on the device, which the
+synchronous leg's do not. The form names the path of the larger triples
+(resident: no larger ones are expected, path tiled).
+  python tools/align_bench.py --n 512 --la 64 --forms resident --async
+  python tools/align_bench.py --n 256 --la 128 --forms tiled --async
 A library without tsa_align_batch (an older build named by TSA_PKG_DIR) runs
 the loop alone: that is how the baseline of a comparison is taken.
 Prints one JSON line: per form the median, min and max of the passes in ms."""
@@ -42,6 +51,9 @@ def main():
     ap.add_argument("--forms", default="resident,plane,loop",
                     help="comma list of loop and align_mode values: resident, plane, tiled, strip, grid")
     ap.add_argument("--tb-bytes", type=int, default=None, help="align_tb_bytes of the batch forms")
+    ap.add_argument("--async", dest="async_", action="store_true",
+                    help="add the tsa_align_batch_async leg of every batch form")
+    ap.add_argument("--train", type=int, default=10, help="calls between the two events of an async pass")
     args = ap.parse_args()
     import bench
     tsa = bench.load_pkg()
@@ -70,12 +82,52 @@ def main():
     def loop():
         return [tsa.align(a, b, c) for a, b, c in trips[:loop_n]]
 
-    forms = {}
+    dev = {}
+
+    def device_leg(mode):
+        """tsa_align_batch_async on device-resident inputs; returns (queue, results)."""
+        import torch
+        if not dev:
+            dev["seqs"], dev["offs"] = torch.from_numpy(seqs).cuda(), torch.from_numpy(offs).cuda()
+            dev["out"] = (torch.zeros(args.n, dtype=torch.int32, device="cuda"),
+                          torch.zeros(len(seqs), dtype=torch.uint8, device="cuda"),
+                          torch.zeros(args.n, dtype=torch.int32, device="cuda"),
+                          torch.zeros(3 * args.n, dtype=torch.int32, device="cuda"))
+        path = "tiled" if mode == "resident" else mode
+        ws_bytes = tsa.align_workspace_size(offs, path=path)[1]
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+        sc, mv, nm, st = dev["out"]
+
+        def queue():
+            tsa.align_batch_async(dev["seqs"].data_ptr(), dev["offs"].data_ptr(), offs, sc.data_ptr(), mv.data_ptr(),
+                                  nm.data_ptr(), st.data_ptr(), ws.data_ptr(), ws_bytes,
+                                  torch.cuda.current_stream().cuda_stream, path=path)
+
+        def results():
+            queue()
+            torch.cuda.synchronize()
+            h = [t.cpu().numpy() for t in (sc, mv, nm, st)]
+            return [(int(h[0][i]), tuple(h[3][3 * i:3 * i + 3]), h[1][int(offs[3 * i]):int(offs[3 * i]) + int(h[2][i])])
+                    for i in range(args.n)]
+
+        def timed():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(args.train):
+                queue()
+            t1.record()
+            t1.synchronize()
+            return t0.elapsed_time(t1) / args.train
+        return results, timed
+
+    forms, timers = {}, {}
     for f in args.forms.split(","):
         if f == "loop":
             forms[f] = loop
         elif have_batch:
             forms[f] = batch(f)
+            if args.async_ and f != "plane" and hasattr(tsa, "align_batch_async"):
+                forms[f + "_async"], timers[f + "_async"] = device_leg(f)
     out, refused = {}, {}
     for f, fn in list(forms.items()):                # first call: also the cross-check
         try:
@@ -91,9 +143,12 @@ def main():
     times = {f: [] for f in forms}
     for k in range(args.warmup + args.passes):
         for f, fn in forms.items():
-            t0 = time.perf_counter()
-            fn()
-            dt = (time.perf_counter() - t0) * 1e3
+            if f in timers:                          # device time of one call of a train
+                dt = timers[f]()
+            else:
+                t0 = time.perf_counter()
+                fn()
+                dt = (time.perf_counter() - t0) * 1e3
             if k >= args.warmup:
                 times[f].append(dt)
     res = {"bench": "align", "n": args.n, "shape": [la, lb, lc], "related": bool(args.related),
@@ -101,6 +156,8 @@ def main():
            "version": tsa.version()}
     if args.tb_bytes is not None:
         res["tb_bytes"] = args.tb_bytes
+    if timers:
+        res["train"] = args.train
     for f, why in refused.items():
         res[f + "_error"] = why
     for f, ts in times.items():
