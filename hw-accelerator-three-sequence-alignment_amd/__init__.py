@@ -66,6 +66,7 @@ EXPORTS = (
     "tsa_score_gpu_multi", "tsa_score_batch_devices", "tsa_set_override", "tsa_get_overrides",
     "tsa_kernel_launch_count", "tsa_align_batch", "tsa_describe_align_plan", "tsa_align_batch_lowmem",
     "tsa_align_batch_grid", "tsa_align_workspace_size", "tsa_align_batch_async", "tsa_align_rows_async",
+    "tsa_align_batch_ends",
 )
 
 # Plan overrides the library accepts (tsa_set_override; include/trialign.h).
@@ -81,6 +82,11 @@ SCORE_UNCERTIFIED = -(2 ** 31) + 1
 # (A, B, C) it consumes -- the predecessor offsets of src/PE_1cyc.v:164-218.
 MOVES = ("M", "Ix", "Iy", "Iz", "Ixy", "Iyz", "Ixz")
 MOVE_CONSUMES = ((1, 1, 1), (1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (0, 1, 1), (1, 0, 1))
+
+# Where an alignment may end in align_batch_ends (TSA_END_*): at the corner
+# (la,lb,lc) as everywhere else, on a far face, or at any cell.
+END_CORNER, END_FACE, END_ANY = 0, 1, 2
+END_MODES = {"corner": END_CORNER, "face": END_FACE, "any": END_ANY}
 
 # The path of the larger triples in tsa_align_batch_async (TSA_ALIGN_PATH_*).
 ALIGN_PATHS = {"tiled": 0, "strip": 1, "grid": 2}
@@ -156,6 +162,8 @@ def _load_lib() -> ctypes.CDLL:
                                     ctypes.c_int32]
     lib.tsa_align_batch_lowmem.argtypes = lib.tsa_align_batch.argtypes
     lib.tsa_align_batch_grid.argtypes = lib.tsa_align_batch.argtypes
+    lib.tsa_align_batch_ends.argtypes = [u8p, i64p, ctypes.c_int32, pp, ctypes.c_int32, i32p, u8p, i32p, i32p, i32p,
+                                         ctypes.c_int32]
     szp = ctypes.POINTER(ctypes.c_size_t)
     lib.tsa_align_workspace_size.argtypes = [i64p, ctypes.c_int32, pp, ctypes.c_int32, szp, szp]
     lib.tsa_align_batch_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, i64p, ctypes.c_int32, pp,
@@ -188,7 +196,7 @@ def _load_lib() -> ctypes.CDLL:
                  "tsa_score_gpu_multi", "tsa_score_batch_devices", "tsa_set_override",
                  "tsa_get_overrides", "tsa_align_batch", "tsa_describe_align_plan",
                  "tsa_align_batch_lowmem", "tsa_align_batch_grid", "tsa_align_workspace_size",
-                 "tsa_align_batch_async", "tsa_align_rows_async"):
+                 "tsa_align_batch_async", "tsa_align_rows_async", "tsa_align_batch_ends"):
         getattr(lib, name).restype = ctypes.c_int
     return lib
 
@@ -429,6 +437,48 @@ def align_batch(triples=None, params: Optional[TsaParams] = None, device: int = 
         out.append((int(sc[i]), tuple(int(v) for v in st[3 * i:3 * i + 3]),
                     mv[m0:m0 + int(nm[i])].copy()))
     return out
+
+
+def align_batch_ends(triples=None, params: Optional[TsaParams] = None, end: str | int = "any", device: int = 0,
+                     seqs: Optional[np.ndarray] = None, offsets: Optional[np.ndarray] = None) -> list:
+    """``align_batch`` with a free end (tsa_align_batch_ends): a list of
+    ``(score, start, moves, end)``, one per triple in the caller's order.
+
+    ``end`` says which cells may end the path: ``"corner"`` (``END_CORNER``)
+    the cell (la, lb, lc), which is ``align_batch``'s result with
+    ``end == (la, lb, lc)``; ``"face"`` (``END_FACE``) the cells where one
+    sequence is used up (overlap alignment); ``"any"`` (``END_ANY``) every
+    cell (the best-scoring triple of prefixes). The end cell (x1, y1, z1) is
+    the candidate with the largest MAX7 -- ties go to the smallest x, then y,
+    then z, and to the lowest state -- ``score`` is that MAX7 and the
+    alignment covers a[x0:x1], b[y0:y1], c[z0:z1]: the symbols beyond the end
+    are no more aligned than those before the start. ``path_score`` and
+    ``render_alignment`` work from ``start`` and ``moves`` alone, so they take
+    these results as they are. Under "face" and "any" the larger triples
+    always take the tiled resident kernel, and ``align_mode`` set to plane,
+    strip or grid raises ``TsaError(TSA_EINVAL)``."""
+    mode = END_MODES.get(end, end) if isinstance(end, str) else end
+    if isinstance(mode, (str, bool)) or not isinstance(mode, (int, np.integer)):
+        raise TsaError(TSA_EINVAL, f"align_batch_ends(end={end!r})")
+    p = params or TsaParams.default()
+    if seqs is None:
+        seqs, offsets = pack_batch(triples)
+    seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = (len(offsets) - 1) // 3
+    sc = np.zeros(max(n, 1), dtype=np.int32)
+    nm = np.zeros(max(n, 1), dtype=np.int32)
+    st = np.zeros(max(3 * n, 1), dtype=np.int32)
+    en = np.zeros(max(3 * n, 1), dtype=np.int32)
+    mv = np.zeros(max(int(offsets[-1] - offsets[0]) if n else 0, 1), dtype=np.uint8)
+    rc = _lib.tsa_align_batch_ends(_ptr(seqs, ctypes.c_uint8), _ptr(offsets, ctypes.c_int64), n, ctypes.byref(p),
+                                   int(mode), _ptr(sc, ctypes.c_int32), _ptr(mv, ctypes.c_uint8),
+                                   _ptr(nm, ctypes.c_int32), _ptr(st, ctypes.c_int32), _ptr(en, ctypes.c_int32), device)
+    _check(rc, "tsa_align_batch_ends")
+    at = (offsets[0:3 * n:3] - offsets[0]).tolist()
+    return [(s, tuple(s0), mv[m0:m0 + k].copy(), tuple(e))
+            for s, s0, m0, k, e in zip(sc[:n].tolist(), st[:3 * n].reshape(-1, 3).tolist(), at, nm[:n].tolist(),
+                                       en[:3 * n].reshape(-1, 3).tolist())]
 
 
 def penalty_table(params: Optional[TsaParams] = None):

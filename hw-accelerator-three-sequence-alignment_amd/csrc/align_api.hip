@@ -1,5 +1,7 @@
 // align_api.hip -- the traceback entry points of include/trialign.h:
-// tsa_align_batch, tsa_align_batch_lowmem, tsa_align_batch_grid, tsa_align_gpu
+// tsa_align_batch, tsa_align_batch_lowmem, tsa_align_batch_grid, tsa_align_batch_ends
+// (tsa_align_batch with a free end: the resident and the tiled kernel search
+// the end cell as they sweep, tb_walk_ends walks from it), tsa_align_gpu
 // (one triple, always the plane sweep), tsa_describe_align_plan and the
 // device-resident tsa_align_workspace_size, tsa_align_batch_async and
 // tsa_align_rows_async, which plan with the same planner against a caller's
@@ -98,6 +100,7 @@ int align_plan_read(AlignPlan *pl) {
 
 // The path of the over-capacity triples of a group that holds n_over of them.
 AlignPath align_over_path(const AlignPlan &pl, int32_t n_over) {
+  if (pl.end_mode != TSA_END_CORNER) return ALIGN_TILED;  // tsa_align_batch_ends: whatever their number
   if (pl.mode == ALIGN_MODE_TILED) return ALIGN_TILED;
   if (pl.mode == ALIGN_MODE_STRIP) return ALIGN_STRIP;
   if (pl.mode == ALIGN_MODE_GRID) return ALIGN_GRID;
@@ -213,25 +216,34 @@ struct AlignDev {
   uint32_t *tb;
   void *faces, *ws;
   int32_t *walk;  // the walker records of a chunk's strip or grid triples
+  // The end records of the chunk under tsa_align_batch_ends (TSA_END_FACE,
+  // TSA_END_ANY), ALIGN_END_REC words a triple; they lie on final7, which the
+  // kernels of those modes do not write.
+  int32_t *endrec;
 };
 
 // Queues the sweeps and walks of chunk c on stream s.
 int align_queue_chunk(const AlignChunk &c, const AlignPlan &pl, const KParams &kp, const AlignDev &d, hipStream_t s) {
   const int32_t m = c.i1 - c.i0, mr = m - c.n_over;
   int rc = TSA_OK;
-  if (mr && (rc = align_launch_resident(d.seqs, d.off, mr, c.max_pos, c.lds, kp, d.scores, d.final7, d.tb, d.tboff, s)))
+  if (mr && (rc = align_launch_resident(d.seqs, d.off, mr, c.max_pos, c.lds, kp, d.scores, d.final7, d.tb, d.tboff, s,
+                                        pl.end_mode, d.endrec)))
     return rc;
   if (c.tiled)
     rc = align_launch_tiled(d.seqs, d.off + 3 * (size_t)mr, c.n_over, pl.tymax, pl.tzmax, c.tile_pos, c.tile_lds, kp,
                             d.scores + mr, d.final7 + (size_t)NSTATE * mr, d.tb, d.tboff + mr, d.faces,
-                            d.faceoff + mr, s);
+                            d.faceoff + mr, s, pl.end_mode,
+                            pl.end_mode != TSA_END_CORNER ? d.endrec + (size_t)ALIGN_END_REC * mr : nullptr);
   else if (c.n_over && !c.strip && !c.grid)
     rc = plane_launch_batch(d.seqs, d.off + 3 * (size_t)mr, c.n_over, c.mla, c.mlb, c.mlc, kp, d.scores + mr,
                             d.final7 + (size_t)NSTATE * mr, d.ws, c.ws, s, d.tb, d.tboff + mr);
   if (rc) return rc;
   // the strip and grid triples are walked segment by segment below; every other one has its whole cube
   const int32_t mw = c.strip || c.grid ? mr : m;
-  if (mw)
+  if (mw && pl.end_mode != TSA_END_CORNER)
+    hipLaunchKernelGGL(tb_walk_ends, dim3((mw + 63) / 64), dim3(64), 0, s, d.tb, d.tboff, d.off, mw, d.endrec,
+                       d.moves, d.info);
+  else if (mw)
     hipLaunchKernelGGL(tb_walk_batch, dim3((mw + 63) / 64), dim3(64), 0, s, d.tb, d.tboff, d.off, mw, d.final7,
                        d.moves, d.info);
   if (c.strip) {
@@ -269,9 +281,10 @@ int align_queue_chunk(const AlignChunk &c, const AlignPlan &pl, const KParams &k
 }
 
 // The traceback of n validated triples on the current device: plan pl, chunks
-// of at most `budget` bytes of pointer cubes. Outputs as tsa_align_batch's.
+// of at most `budget` bytes of pointer cubes. Outputs as tsa_align_batch's;
+// ends (tsa_align_batch_ends, null otherwise) gets the end cell of every triple.
 int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KParams &kp, const AlignPlan &pl,
-              size_t budget, int32_t *scores, uint8_t *moves, int32_t *n_moves, int32_t *starts) {
+              size_t budget, int32_t *scores, uint8_t *moves, int32_t *n_moves, int32_t *starts, int32_t *ends) {
   const std::vector<AlignTriple> T = align_plan_triples(offsets, n, pl, false);
   std::vector<AlignChunk> chunks;
   int rc = align_plan_chunks(T, pl, budget, &chunks);
@@ -325,6 +338,7 @@ int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KPar
     d.seqs = d_seqs, d.off = d_meta, d.tboff = d_meta + 3 * (size_t)m + 1, d.faceoff = d.tboff + m;
     d.scores = d_res, d.final7 = d_res + m, d.info = d_res + 8 * (size_t)m;
     d.moves = d_moves, d.tb = d_tb, d.faces = d_faces, d.ws = d_ws, d.walk = d_walk;
+    d.endrec = d.final7;
     if (hipMemcpyAsync(d_seqs, h_seqs.data(), (size_t)pos, hipMemcpyHostToDevice, B.s) != hipSuccess ||
         hipMemcpyAsync(d_meta, h_meta.data(), sizeof(int64_t) * (5 * (size_t)m + 1), hipMemcpyHostToDevice, B.s) !=
             hipSuccess)
@@ -341,6 +355,13 @@ int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KPar
       const int32_t *info = h_res.data() + 8 * (size_t)m + 4 * (size_t)j;
       const int64_t len = offsets[3 * (int64_t)i + 3] - offsets[3 * (int64_t)i];
       if (info[0] < 1 || info[0] > len) return TSA_EINTERNAL;
+      if (ends) {
+        const AlignTriple &t = T[i];
+        const int32_t *rec = h_res.data() + m + (size_t)ALIGN_END_REC * j;  // on final7, see AlignDev
+        const int32_t corner[3] = {t.la, t.lb, t.lc};
+        const int32_t *e = pl.end_mode != TSA_END_CORNER ? rec : corner;
+        for (int k = 0; k < 3; ++k) ends[3 * (int64_t)i + k] = e[k];
+      }
       std::memcpy(moves + (offsets[3 * (int64_t)i] - offsets[0]), h_moves.data() + h_off[3 * j], (size_t)info[0]);
       scores[i] = h_res[j];
       n_moves[i] = info[0];
@@ -460,8 +481,10 @@ namespace {
 // tsa_align_batch, tsa_align_batch_lowmem and tsa_align_batch_grid:
 // validation, plan, budget, run. unset: the plan mode unless align_mode is set
 // (auto, strip under lowmem, grid).
+// tsa_align_batch_ends: the same with end_mode and ends (null elsewhere).
 int align_batch_entry(const uint8_t *seqs, const int64_t *offsets, int32_t n, const tsa_params *p, int32_t *scores,
-                      uint8_t *moves, int32_t *n_moves, int32_t *starts, int32_t device, AlignMode unset) {
+                      uint8_t *moves, int32_t *n_moves, int32_t *starts, int32_t device, AlignMode unset,
+                      int32_t end_mode = TSA_END_CORNER, int32_t *ends = nullptr) {
   if (!seqs || !offsets || !scores || !moves || !n_moves || !starts || n < 0 || !params_ok(p)) return TSA_EINVAL;
   for (int32_t i = 0; i < n; ++i) {
     const int64_t *o = offsets + 3 * (int64_t)i;
@@ -471,15 +494,27 @@ int align_batch_entry(const uint8_t *seqs, const int64_t *offsets, int32_t n, co
     if (rc) return rc;
   }
   if (n == 0) return TSA_OK;
+  AlignPlan pl;
+  int rc = TSA_OK;
+  if (end_mode != TSA_END_CORNER) {
+    // the end search is the resident and the tiled kernel's: no plane sweep, no
+    // strips, no grid -- a matter of the arguments, so it is found without a device
+    if ((rc = align_plan_read(&pl))) return rc;
+    if (pl.mode == ALIGN_MODE_PLANE || pl.mode == ALIGN_MODE_STRIP || pl.mode == ALIGN_MODE_GRID) return TSA_EINVAL;
+  }
   const int nd = tsa_device_count();
   if (nd <= 0) return TSA_ENODEV;
   if (device < 0 || device >= nd) return TSA_ENODEV;
   KParams kp;
-  int rc = build_kparams(p, &kp);
-  if (rc) return rc;
-  AlignPlan pl;
+  if ((rc = build_kparams(p, &kp))) return rc;
   if ((rc = align_plan_read(&pl))) return rc;
   if (!pl.mode_set) pl.mode = unset;
+  pl.end_mode = end_mode;
+  if (end_mode != TSA_END_CORNER)
+    for (int32_t i = 0; i < n; ++i) {  // a cube the key cannot number is far beyond any device's memory
+      const int64_t *o = offsets + 3 * (int64_t)i;
+      if (!align_end_key_fits((int32_t)(o[1] - o[0]), (int32_t)(o[2] - o[1]), (int32_t)(o[3] - o[2]))) return TSA_ENOMEM;
+    }
   if (hipSetDevice(device) != hipSuccess) return TSA_EDEVICE;
   // The pointer-cube budget of a chunk: align_tb_bytes, or half of the device
   // memory free at the call (the other half is left to the caller's own
@@ -497,7 +532,7 @@ int align_batch_entry(const uint8_t *seqs, const int64_t *offsets, int32_t n, co
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return TSA_EDEVICE;
     budget = free_b / 2;
   }
-  return align_run(seqs, offsets, n, kp, pl, budget, scores, moves, n_moves, starts);
+  return align_run(seqs, offsets, n, kp, pl, budget, scores, moves, n_moves, starts, ends);
 }
 }  // namespace
 
@@ -516,6 +551,13 @@ int tsa_align_batch_lowmem(const uint8_t *seqs, const int64_t *offsets, int32_t 
 int tsa_align_batch_grid(const uint8_t *seqs, const int64_t *offsets, int32_t n, const tsa_params *p,
                          int32_t *scores, uint8_t *moves, int32_t *n_moves, int32_t *starts, int32_t device) {
   return align_batch_entry(seqs, offsets, n, p, scores, moves, n_moves, starts, device, ALIGN_MODE_GRID);
+}
+
+int tsa_align_batch_ends(const uint8_t *seqs, const int64_t *offsets, int32_t n, const tsa_params *p, int32_t end_mode,
+                         int32_t *scores, uint8_t *moves, int32_t *n_moves, int32_t *starts, int32_t *ends,
+                         int32_t device) {
+  if (!ends || end_mode < TSA_END_CORNER || end_mode > TSA_END_ANY) return TSA_EINVAL;
+  return align_batch_entry(seqs, offsets, n, p, scores, moves, n_moves, starts, device, ALIGN_MODE_AUTO, end_mode, ends);
 }
 
 int tsa_align_workspace_size(const int64_t *h_offsets, int32_t n, const tsa_params *p, int32_t path,
@@ -571,6 +613,7 @@ int tsa_align_batch_async(const uint8_t *d_seqs, const int64_t *d_offsets, const
     // the faces (16-byte cells) first, then the cubes (words): c.face + c.cube = c.need bytes
     d.faces = w + f.total, d.tb = (uint32_t *)(w + f.total + c.face), d.ws = nullptr;
     d.walk = (int32_t *)(w + f.walk) + (size_t)ALIGN_WALK_REC * c.i0;
+    d.endrec = nullptr;  // no end-free form on this path
     align_launch_meta(d_offsets, c.i0, m, A.pl, b, s);
     align_launch_pack(d_seqs, d_offsets, m, b, s);
     if ((rc = align_queue_chunk(c, A.pl, kp, d, s))) return rc;

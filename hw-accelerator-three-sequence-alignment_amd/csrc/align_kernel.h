@@ -60,9 +60,31 @@ __host__ __device__ inline size_t align_cube_bytes(int32_t la, int32_t lb, int32
 // One launch for n triples that all fit, through launch_with_lds (so
 // tsa_kernel_launch_count counts it): max_pos = the largest lb*lc and lds =
 // the largest align_resident_lds of the batch.
+// end_mode = TSA_END_FACE / TSA_END_ANY (tsa_align_batch_ends): the kernel
+// searches the end cell as it sweeps and writes the triple's end record
+// (below) to d_endrec[5t] and its MAX7 to d_scores[t]; d_final7 is not written.
 int align_launch_resident(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, int64_t max_pos, size_t lds,
                           const KParams &kp, int32_t *d_scores, int32_t *d_final7, uint32_t *d_tb,
-                          const int64_t *d_tb_off, hipStream_t stream);
+                          const int64_t *d_tb_off, hipStream_t stream, int32_t end_mode = TSA_END_CORNER,
+                          int32_t *d_endrec = nullptr);
+
+// The end record of a triple under tsa_align_batch_ends, int32 words
+// {x1, y1, z1, state, score}: the cell and the state the path ends in and that
+// cell's MAX7. The kernels find it through a 64-bit key per cell (align_step.h)
+// whose position field holds the cell's number in (x,y,z) order, below la*lb*lc.
+constexpr int ALIGN_END_REC = 5;
+constexpr int ALIGN_END_POS_BITS = 45;
+constexpr uint64_t ALIGN_END_POS_MASK = (1ull << ALIGN_END_POS_BITS) - 1;
+// Every cube whose pointers fit device memory passes: it has more than
+// la*lb*lc words of 4 bytes.
+__host__ __device__ inline bool align_end_key_fits(int32_t la, int32_t lb, int32_t lc) {
+  const uint64_t lim = 1ull << ALIGN_END_POS_BITS, plane = (uint64_t)lb * (uint64_t)lc;  // below 2^62
+  return plane <= lim && (uint64_t)la <= lim / plane;
+}
+// The walks of n triples from their end records, one walker (thread) per
+// triple, otherwise as tb_walk_batch: the cube is indexed with the full lengths.
+__global__ void tb_walk_ends(const uint32_t *tb, const int64_t *tb_off, const int64_t *offs, int32_t n,
+                             const int32_t *endrec, uint8_t *moves, int32_t *info);
 
 // The tiled resident kernel (align_tiled_kernel.hip): one workgroup sweeps a
 // cube whose (y,z) plane does not fit it, tile by tile, the tiles chained
@@ -100,7 +122,7 @@ __host__ __device__ inline size_t align_tiled_face_cells(int32_t la, int32_t lb,
 int align_launch_tiled(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, int32_t tymax, int32_t tzmax,
                        int64_t max_pos, size_t lds, const KParams &kp, int32_t *d_scores, int32_t *d_final7,
                        uint32_t *d_tb, const int64_t *d_tb_off, void *d_faces, const int64_t *d_face_off,
-                       hipStream_t stream);
+                       hipStream_t stream, int32_t end_mode = TSA_END_CORNER, int32_t *d_endrec = nullptr);
 
 // The strip kernel (align_strip_kernel.hip): a strip is one tile row of the
 // tiled kernel, TY rows of y with all of z and x. A forward launch keeps the y
@@ -201,6 +223,7 @@ struct AlignPlan {
   int32_t mode_set = 0;  // align_mode is set
   int32_t capped = 0;    // align_tile is set
   int32_t tymax = ALIGN_TILE_Y, tzmax = ALIGN_TILE_Z;
+  int32_t end_mode = 0;  // TSA_END_FACE / TSA_END_ANY: every over-capacity triple is tiled
 };
 // Over capacity: the triple does not go to the resident kernel as a whole.
 // With align_tile set under align_mode = tiled, strip or grid that is any triple

@@ -44,11 +44,15 @@ constexpr int ALIGN_K = 4;      // positions per thread at most (115 VGPRs of th
 static_assert((int64_t)ALIGN_NT * ALIGN_K == ALIGN_RESIDENT_POS && LDS_MAX == ALIGN_LDS_BYTES,
               "align_kernel.h's capacity of the resident kernel");
 
-template <int K>
+// END = TSA_END_FACE / TSA_END_ANY (tsa_align_batch_ends): every thread keeps
+// the best end key of its cells (align_step.h), the workgroup reduces the keys
+// after the last step and thread 0 writes the end record tb_walk_ends starts
+// from, and the score; final7 is not written.
+template <int K, int END = TSA_END_CORNER>
 __global__ __launch_bounds__(ALIGN_NT) void align_resident_kernel(
     const uint8_t *__restrict__ seqs, const int64_t *__restrict__ offs, KParams kp, uint32_t lds_bytes,
     int32_t *__restrict__ scores, int32_t *__restrict__ final7, uint32_t *__restrict__ tb,
-    const int64_t *__restrict__ tb_off) {
+    const int64_t *__restrict__ tb_off, int32_t *__restrict__ endrec) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int64_t t = blockIdx.x;
   const int64_t o0 = offs[3 * t], o1 = offs[3 * t + 1], o2 = offs[3 * t + 2], o3 = offs[3 * t + 3];
@@ -73,13 +77,26 @@ __global__ __launch_bounds__(ALIGN_NT) void align_resident_kernel(
   for (int k = 0; k < K; ++k) P(k).init(k * nt + tid, lb, lc, sym, sym + lb);
   uint32_t *cube = tb + tb_off[t];
   const int32_t qmax = la + lb + lc;
-  for (int32_t q = 2; q <= qmax; ++q) {
-    const uint4 *rd = (q & 1) ? buf0 : buf1;  // buf[(q-1)&1]
-    uint4 *wr = (q & 1) ? buf1 : buf0;        // buf[q&1]
+  if constexpr (END == TSA_END_CORNER) {
+    for (int32_t q = 2; q <= qmax; ++q) {
+      const uint4 *rd = (q & 1) ? buf0 : buf1;  // buf[(q-1)&1]
+      uint4 *wr = (q & 1) ? buf1 : buf0;        // buf[q&1]
 #pragma unroll
-    for (int k = 0; k < K; ++k)
-      P(k).step(rd, wr, ldz, q, la, 0, 0, lb, lc, cube, kp, t, scores, final7, symA);
-    __syncthreads();
+      for (int k = 0; k < K; ++k)
+        P(k).step(rd, wr, ldz, q, la, 0, 0, lb, lc, cube, kp, t, scores, final7, symA);
+      __syncthreads();
+    }
+  } else {
+    AlignEnd end;
+    for (int32_t q = 2; q <= qmax; ++q) {
+      const uint4 *rd = (q & 1) ? buf0 : buf1;
+      uint4 *wr = (q & 1) ? buf1 : buf0;
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+        P(k).template step<true, END>(rd, wr, ldz, q, la, 0, 0, lb, lc, cube, kp, t, scores, final7, symA, lc, &end);
+      __syncthreads();
+    }
+    align_end_reduce(end, (uint64_t *)smem, tid, nt, lb, lc, endrec + ALIGN_END_REC * t, scores + t);
   }
 }
 
@@ -88,19 +105,30 @@ __global__ __launch_bounds__(ALIGN_NT) void align_resident_kernel(
 // align_resident_fits. d_tb_off[t] is the word offset of triple t's cube.
 int align_launch_resident(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, int64_t max_pos, size_t lds,
                           const KParams &kp, int32_t *d_scores, int32_t *d_final7, uint32_t *d_tb,
-                          const int64_t *d_tb_off, hipStream_t stream) {
+                          const int64_t *d_tb_off, hipStream_t stream, int32_t end_mode, int32_t *d_endrec) {
   if (n <= 0) return TSA_OK;
   if (max_pos < 1 || max_pos > (int64_t)ALIGN_NT * ALIGN_K || lds > LDS_MAX || !d_tb || !d_tb_off) return TSA_EINVAL;
+  if (end_mode < TSA_END_CORNER || end_mode > TSA_END_ANY || (end_mode != TSA_END_CORNER && !d_endrec)) return TSA_EINVAL;
   const int k = max_pos <= ALIGN_NT ? 1 : max_pos <= 2 * ALIGN_NT ? 2 : 4;
   const int nt = (int)(((max_pos + k - 1) / k + 63) / 64 * 64);
   auto launch = [&](auto kfn) {
     return launch_with_lds((const void *)kfn, lds, [&] {
              hipLaunchKernelGGL(kfn, dim3(n), dim3(nt), lds, stream, d_seqs, d_offsets, kp, (uint32_t)lds, d_scores,
-                                d_final7, d_tb, d_tb_off);
+                                d_final7, d_tb, d_tb_off, d_endrec);
            }) == hipSuccess
                ? TSA_OK
                : TSA_EDEVICE;
   };
+  if (end_mode == TSA_END_FACE) {
+    if (k == 1) return launch(align_resident_kernel<1, TSA_END_FACE>);
+    if (k == 2) return launch(align_resident_kernel<2, TSA_END_FACE>);
+    return launch(align_resident_kernel<4, TSA_END_FACE>);
+  }
+  if (end_mode == TSA_END_ANY) {
+    if (k == 1) return launch(align_resident_kernel<1, TSA_END_ANY>);
+    if (k == 2) return launch(align_resident_kernel<2, TSA_END_ANY>);
+    return launch(align_resident_kernel<4, TSA_END_ANY>);
+  }
   if (k == 1) return launch(align_resident_kernel<1>);
   if (k == 2) return launch(align_resident_kernel<2>);
   return launch(align_resident_kernel<4>);

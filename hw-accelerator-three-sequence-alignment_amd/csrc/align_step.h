@@ -14,6 +14,7 @@
 
 #include <type_traits>
 
+#include "align_kernel.h"
 #include "literal_cell.h"
 
 namespace tsa {
@@ -40,6 +41,64 @@ __device__ __forceinline__ auto align_sym_a(L &&lds, PA &&sA, PS &&seqs, O &&o0,
     i = min(max(i, 0), la - 1);
     return lds ? (int)sA[i] : (int)tsa_sym(seqs, o0 + i, kp.packed);
   };
+}
+
+// The end search of tsa_align_batch_ends (TSA_END_FACE, TSA_END_ANY): the
+// candidate cell whose MAX7 is largest ends the path; ties go to the smallest
+// x, then y, then z, and to the lowest state. One totally ordered 64-bit key
+// says all of it, so a plain max over the cells in any order is the rule:
+//   [63:48] MAX7 + 32768 (a state is an int16, pack7)
+//   [47:3]  ~pos, pos = ((x-1)*lb + (y-1))*lc + (z-1) < la*lb*lc, the cell's
+//           number in (x,y,z) order: no width to carry but lb and lc, which the
+//           kernels hold anyway. A pointer cube has more words than that, so
+//           every cube that fits device memory fits the 45 bits
+//           (align_end_key_fits).
+//   [2:0]   7 - the lowest state that reaches the MAX7
+// The running best of a thread, across its positions and tiles; 0 = none yet.
+struct AlignEnd {
+  uint64_t best = 0;
+  __device__ __forceinline__ void fold(const int32_t (&S)[7], int32_t x, int32_t y, int32_t z, int32_t lb,
+                                       int32_t lc) {
+    // Nothing of the key is to be hoisted out of the step loop into registers
+    // of its own (the cell's number less its x term is invariant there): that
+    // alone spilled the widest instantiations.
+    asm volatile("" : "+v"(y), "+v"(z));
+    int32_t m = S[0] * 8 + 7;  // the max of (state value, 7 - index) pairs: the lowest index of the largest value
+#pragma unroll
+    for (int s = 1; s < NSTATE; ++s) m = max(m, S[s] * 8 + (7 - s));
+    const uint64_t pos = ((uint64_t)(uint32_t)(x - 1) * (uint32_t)lb + (uint32_t)(y - 1)) * (uint32_t)lc +
+                         (uint32_t)(z - 1);
+    const uint64_t key = ((uint64_t)(uint32_t)((m >> 3) + 32768) << 48) | ((~pos & ALIGN_END_POS_MASK) << 3) |
+                         (uint32_t)(m & 7);
+    best = max(best, key);
+  }
+};
+
+// The workgroup's best key after its last step (whose barrier lies behind, so
+// slots, LDS for one key per wave, may be the cell buffers): a wave reduce,
+// then thread 0 over the waves' keys, which writes the triple's end record
+// rec = {x1, y1, z1, state, score} and its score.
+__device__ __forceinline__ void align_end_reduce(const AlignEnd &end, uint64_t *slots, int tid, int nt, int32_t lb,
+                                                 int32_t lc, int32_t *rec, int32_t *score) {
+  uint64_t k = end.best;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const uint32_t lo = __shfl_xor((uint32_t)k, d, 64), hi = __shfl_xor((uint32_t)(k >> 32), d, 64);
+    k = max(k, ((uint64_t)hi << 32) | lo);
+  }
+  if ((tid & 63) == 0) slots[tid >> 6] = k;
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < nt / 64; ++w) k = max(k, slots[w]);
+    const uint64_t pos = ~(k >> 3) & ALIGN_END_POS_MASK, row = pos / (uint32_t)lc;
+    const int32_t sc = (int32_t)(k >> 48) - 32768;
+    rec[0] = (int32_t)(row / (uint32_t)lb) + 1;
+    rec[1] = (int32_t)(row % (uint32_t)lb) + 1;
+    rec[2] = (int32_t)(pos % (uint32_t)lc) + 1;
+    rec[3] = 7 - (int32_t)(k & 7u);
+    rec[4] = sc;
+    *score = sc;
+  }
 }
 
 // One (y,z) position of a thread, in the coordinates of its tile: a view of
@@ -76,10 +135,15 @@ struct AlignPos {
                                        int64_t t, int32_t *scores, int32_t *final7, const SymA &symA) {
     step<TB>(rd, wr, ldz, q, la, y0, z0, lb, lc, cube, kp, t, scores, final7, symA, lc);
   }
-  template <bool TB = true, class SymA>
+  // END = TSA_END_FACE / TSA_END_ANY (the kernels of tsa_align_batch_ends):
+  // a cell that may end the path also folds its end key into the thread's
+  // running best `end`, and the corner gives no score and no final states --
+  // the reduction of the keys does (align_end_reduce).
+  template <bool TB = true, int END = 0, class SymA>
   __device__ __forceinline__ void step(const uint4 *rd, uint4 *wr, int32_t ldz, int32_t q, int32_t la, int32_t y0,
                                        int32_t z0, int32_t lb, int32_t lc, uint32_t *cube, const KParams &kp,
-                                       int64_t t, int32_t *scores, int32_t *final7, const SymA &symA, int32_t cld) {
+                                       int64_t t, int32_t *scores, int32_t *final7, const SymA &symA, int32_t cld,
+                                       AlignEnd *end = nullptr) {
     const int32_t sh = kp.wrap_shift;
     const int32_t y = (int32_t)(meta & 0x1FFFu), z = (int32_t)((meta >> 13) & 0x1FFFu);
     const int32_t x = q - y - z;
@@ -113,7 +177,9 @@ struct AlignPos {
         wr[idx] = pack7(S);
         if constexpr (TB) {
           cube[tb_index(x, y0 + y, z0 + z, la, cld)] = w;
-          if (x == la && y0 + y == lb && z0 + z == lc) {  // FINAL_MAX, src/TriAlign_1cyc.v:141-142
+          if constexpr (END != 0) {
+            if (END == TSA_END_ANY || x == la || y0 + y == lb || z0 + z == lc) end->fold(S, x, y0 + y, z0 + z, lb, lc);
+          } else if (x == la && y0 + y == lb && z0 + z == lc) {  // FINAL_MAX, src/TriAlign_1cyc.v:141-142
             int32_t m = S[0];
 #pragma unroll
             for (int s = 1; s < NSTATE; ++s) m = max(m, S[s]);

@@ -50,12 +50,14 @@ bool align_tile_fits(int32_t ty, int32_t tz) {
   return ty >= 1 && tz >= 1 && (int64_t)ty * tz <= (int64_t)TILED_NT * TILED_K && align_resident_fits(1, ty, tz);
 }
 
-template <int K>
+// END = TSA_END_FACE / TSA_END_ANY (tsa_align_batch_ends): as the resident
+// kernel's, the running best end key of a thread kept across the tiles.
+template <int K, int END = TSA_END_CORNER>
 __global__ __launch_bounds__(TILED_NT) void align_tiled_kernel(
     const uint8_t *__restrict__ seqs, const int64_t *__restrict__ offs, KParams kp, uint32_t lds_bytes,
     int32_t tymax, int32_t tzmax, int32_t *__restrict__ scores, int32_t *__restrict__ final7,
     uint32_t *__restrict__ tb, const int64_t *__restrict__ tb_off, uint4 *faces,
-    const int64_t *__restrict__ face_off) {
+    const int64_t *__restrict__ face_off, int32_t *__restrict__ endrec) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int64_t t = blockIdx.x;
   const int64_t o0 = offs[3 * t], o1 = offs[3 * t + 1], o2 = offs[3 * t + 2], o3 = offs[3 * t + 3];
@@ -74,6 +76,7 @@ __global__ __launch_bounds__(TILED_NT) void align_tiled_kernel(
   const int64_t ysz = (int64_t)la * (lc + 1), zsz = (int64_t)la * TY;
   uint4 *yf = faces + face_off[t], *zf = yf + 2 * ysz;
   uint32_t *cube = tb + tb_off[t];
+  [[maybe_unused]] AlignEnd end;  // the running best of the thread, kept across the tiles
   for (int32_t ty = 0; ty < tg.nty; ++ty)
     for (int32_t tz = 0; tz < tg.ntz; ++tz) {
       const int32_t y0 = ty * TY, z0 = tz * TZ;
@@ -100,8 +103,13 @@ __global__ __launch_bounds__(TILED_NT) void align_tiled_kernel(
         const uint4 *rd = (q & 1) ? buf0 : buf1;  // buf[(q-1)&1]
         uint4 *wr = (q & 1) ? buf1 : buf0;        // buf[q&1]
 #pragma unroll
-        for (int k = 0; k < K; ++k)
-          P(k).step(rd, wr, ldz, q, la, y0, z0, lb, lc, cube, kp, t, scores, final7, symA);
+        for (int k = 0; k < K; ++k) {
+          if constexpr (END == TSA_END_CORNER)
+            P(k).step(rd, wr, ldz, q, la, y0, z0, lb, lc, cube, kp, t, scores, final7, symA);
+          else
+            P(k).template step<true, END>(rd, wr, ldz, q, la, y0, z0, lb, lc, cube, kp, t, scores, final7, symA, lc,
+                                          &end);
+        }
         // face work, off the cell's registers: f = 0 the corner, 1 .. tzl row 0
         // and the last local row, tzl+1 .. tzl+tyl column 0 and the last local
         // column. A face position publishes its cell of this step; a position of
@@ -123,6 +131,8 @@ __global__ __launch_bounds__(TILED_NT) void align_tiled_kernel(
         __syncthreads();
       }
     }
+  if constexpr (END != TSA_END_CORNER)
+    align_end_reduce(end, (uint64_t *)smem, tid, nt, lb, lc, endrec + ALIGN_END_REC * t, scores + t);
 }
 
 // One launch for n triples, triple = workgroup, each swept in tiles of at most
@@ -133,8 +143,9 @@ __global__ __launch_bounds__(TILED_NT) void align_tiled_kernel(
 int align_launch_tiled(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, int32_t tymax, int32_t tzmax,
                        int64_t max_pos, size_t lds, const KParams &kp, int32_t *d_scores, int32_t *d_final7,
                        uint32_t *d_tb, const int64_t *d_tb_off, void *d_faces, const int64_t *d_face_off,
-                       hipStream_t stream) {
+                       hipStream_t stream, int32_t end_mode, int32_t *d_endrec) {
   if (n <= 0) return TSA_OK;
+  if (end_mode < TSA_END_CORNER || end_mode > TSA_END_ANY || (end_mode != TSA_END_CORNER && !d_endrec)) return TSA_EINVAL;
   if (!align_tile_fits(tymax, tzmax) || max_pos < 1 || max_pos > (int64_t)tymax * tzmax || lds > LDS_MAX || !d_tb ||
       !d_tb_off || !d_faces || !d_face_off)
     return TSA_EINVAL;
@@ -143,11 +154,22 @@ int align_launch_tiled(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t 
   auto launch = [&](auto kfn) {
     return launch_with_lds((const void *)kfn, lds, [&] {
              hipLaunchKernelGGL(kfn, dim3(n), dim3(nt), lds, stream, d_seqs, d_offsets, kp, (uint32_t)lds, tymax,
-                                tzmax, d_scores, d_final7, d_tb, d_tb_off, (uint4 *)d_faces, d_face_off);
+                                tzmax, d_scores, d_final7, d_tb, d_tb_off, (uint4 *)d_faces, d_face_off,
+                                d_endrec);
            }) == hipSuccess
                ? TSA_OK
                : TSA_EDEVICE;
   };
+  if (end_mode == TSA_END_FACE) {
+    if (k == 1) return launch(align_tiled_kernel<1, TSA_END_FACE>);
+    if (k == 2) return launch(align_tiled_kernel<2, TSA_END_FACE>);
+    return launch(align_tiled_kernel<3, TSA_END_FACE>);
+  }
+  if (end_mode == TSA_END_ANY) {
+    if (k == 1) return launch(align_tiled_kernel<1, TSA_END_ANY>);
+    if (k == 2) return launch(align_tiled_kernel<2, TSA_END_ANY>);
+    return launch(align_tiled_kernel<3, TSA_END_ANY>);
+  }
   if (k == 1) return launch(align_tiled_kernel<1>);
   if (k == 2) return launch(align_tiled_kernel<2>);
   return launch(align_tiled_kernel<3>);

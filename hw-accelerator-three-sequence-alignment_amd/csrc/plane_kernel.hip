@@ -226,23 +226,21 @@ __global__ __launch_bounds__(64 * PLANE_TY) void plane_step_kernel(
   }
 }
 
-// Follow the pointers back from cell (la,lb,lc) (<= la+lb+lc dependent
-// loads). moves[] gets the states from the end backwards; info = {moves, x0,
-// y0, z0} where (x0,y0,z0) is the face cell the path leaves.
-__device__ __forceinline__ void walk_back(const uint32_t *__restrict__ tb, const int32_t *__restrict__ final7,
-                                          int32_t la, int32_t lb, int32_t lc, uint8_t *__restrict__ moves,
+// Follow the pointers back from cell (x,y,z) in state T of a cube of lengths
+// la and lc (<= x+y+z dependent loads). moves[] gets the states from the end
+// backwards; info = {moves, x0, y0, z0} where (x0,y0,z0) is the face cell the
+// path leaves.
+__device__ __forceinline__ void walk_back(const uint32_t *__restrict__ tb, int32_t T, int32_t x, int32_t y, int32_t z,
+                                          int32_t la, int32_t lc, uint8_t *__restrict__ moves,
                                           int32_t *__restrict__ info) {
-  // final MAX7 (src/TriAlign_1cyc.v:141-142): lowest state index on ties
-  int32_t T = 0;
-  for (int s = 1; s < NSTATE; ++s)
-    if (final7[s] > final7[T]) T = s;
   constexpr int DX[7] = {1, 1, 0, 0, 1, 0, 1}, DY[7] = {1, 0, 1, 0, 1, 1, 0},
                 DZ[7] = {1, 0, 0, 1, 0, 1, 1};  // predecessor offsets per state
-  int32_t x = la, y = lb, z = lc, n = 0;
+  const int32_t bound = x + y + z;
+  int32_t n = 0;
   for (;;) {
     moves[n++] = (uint8_t)T;
     const int32_t px = x - DX[T], py = y - DY[T], pz = z - DZ[T];
-    if (px == 0 || py == 0 || pz == 0 || n >= la + lb + lc) {
+    if (px == 0 || py == 0 || pz == 0 || n >= bound) {
       x = px;
       y = py;
       z = pz;
@@ -257,6 +255,16 @@ __device__ __forceinline__ void walk_back(const uint32_t *__restrict__ tb, const
   info[1] = x;
   info[2] = y;
   info[3] = z;
+}
+// From cell (la,lb,lc), in the state of the final MAX7.
+__device__ __forceinline__ void walk_back(const uint32_t *__restrict__ tb, const int32_t *__restrict__ final7,
+                                          int32_t la, int32_t lb, int32_t lc, uint8_t *__restrict__ moves,
+                                          int32_t *__restrict__ info) {
+  // final MAX7 (src/TriAlign_1cyc.v:141-142): lowest state index on ties
+  int32_t T = 0;
+  for (int s = 1; s < NSTATE; ++s)
+    if (final7[s] > final7[T]) T = s;
+  walk_back(tb, T, la, lb, lc, la, lc, moves, info);
 }
 
 // The single-triple walk (one thread).
@@ -282,6 +290,34 @@ __global__ __launch_bounds__(64) void tb_walk_batch(const uint32_t *__restrict__
   uint8_t *mv = moves + o0;
   walk_back(tb + tb_off[t], final7 + t * NSTATE, (int32_t)(o1 - o0), (int32_t)(o2 - o1), (int32_t)(o3 - o2), mv,
             info + 4 * t);
+  for (int32_t i = 0, j = info[4 * t] - 1; i < j; ++i, --j) {
+    const uint8_t m = mv[i];
+    mv[i] = mv[j];
+    mv[j] = m;
+  }
+}
+
+// tb_walk_batch from the end records of tsa_align_batch_ends: triple t's walk
+// starts at cell endrec[5t .. 5t+2] in state endrec[5t+3] (align_kernel.h's
+// ALIGN_END_REC words {x1, y1, z1, state, score}); the cube is indexed with the
+// full lengths. A record outside the cube (never written) gives info[4t] = 0,
+// which the host reports as TSA_EINTERNAL.
+__global__ __launch_bounds__(64) void tb_walk_ends(const uint32_t *__restrict__ tb,
+                                                   const int64_t *__restrict__ tb_off,
+                                                   const int64_t *__restrict__ offs, int32_t n,
+                                                   const int32_t *__restrict__ endrec,
+                                                   uint8_t *__restrict__ moves, int32_t *__restrict__ info) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const int64_t o0 = offs[3 * t], o1 = offs[3 * t + 1], o2 = offs[3 * t + 2], o3 = offs[3 * t + 3];
+  const int32_t la = (int32_t)(o1 - o0), lb = (int32_t)(o2 - o1), lc = (int32_t)(o3 - o2);
+  const int32_t *r = endrec + ALIGN_END_REC * t;
+  if (r[0] < 1 || r[0] > la || r[1] < 1 || r[1] > lb || r[2] < 1 || r[2] > lc || r[3] < 0 || r[3] >= NSTATE) {
+    info[4 * t] = 0;
+    return;
+  }
+  uint8_t *mv = moves + o0;
+  walk_back(tb + tb_off[t], r[3], r[0], r[1], r[2], la, lc, mv, info + 4 * t);
   for (int32_t i = 0, j = info[4 * t] - 1; i < j; ++i, --j) {
     const uint8_t m = mv[i];
     mv[i] = mv[j];

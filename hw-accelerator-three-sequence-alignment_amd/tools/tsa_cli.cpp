@@ -2,7 +2,7 @@
 // "TriAlign Score: <n>" (src/TriAlign_tb.sv:339-341).
 //   tsa A.dat B.dat C.dat [--kernel auto|plane|pencil] [--device N]
 //       [--s3 rtl|sop] [--bits B] [--match M --mismatch X --go O --ge E]
-//       [--states] [--align]
+//       [--states] [--align [--end corner|face|any]]
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -15,13 +15,15 @@ static int usage() {
           "usage: tsa A B C [--kernel auto|plane|pencil] [--device N] [--s3 rtl|sop]\n"
           "           [--bits B] [--match M] [--mismatch X] [--go O] [--ge E] [--states]\n"
           "           [--align]   (also print the optimal alignment; tsa_align_gpu)\n"
+          "           [--end corner|face|any]   (with --align: where the path may end; face and any\n"
+          "                                      go through tsa_align_batch_ends and print the end)\n"
           "A/B/C: dat files (one symbol 0..4 per line) or FASTA (A=0 T=1 C=2 G=3 N=4)\n");
   return 2;
 }
 
 int main(int argc, char **argv) {
   const char *files[3];
-  int nf = 0, device = 0, kernel = TSA_KERNEL_AUTO, states = 0, align = 0;
+  int nf = 0, device = 0, kernel = TSA_KERNEL_AUTO, states = 0, align = 0, end = TSA_END_CORNER;
   tsa_params p;
   tsa_default_params(&p);
   for (int i = 1; i < argc; ++i) {
@@ -40,11 +42,19 @@ int main(int argc, char **argv) {
     else if (!strcmp(a, "--ge")) { const char *v = next(); if (!v) return usage(); p.gap_extend = atoi(v); }
     else if (!strcmp(a, "--states")) states = 1;
     else if (!strcmp(a, "--align")) align = 1;
+    else if (!strcmp(a, "--end")) {
+      const char *v = next();
+      if (!v) return usage();
+      if (!strcmp(v, "corner")) end = TSA_END_CORNER;
+      else if (!strcmp(v, "face")) end = TSA_END_FACE;
+      else if (!strcmp(v, "any")) end = TSA_END_ANY;
+      else return usage();
+    }
     else if (a[0] == '-' && a[1] == '-') return usage();
     else if (nf < 3) files[nf++] = a;
     else return usage();
   }
-  if (nf != 3) return usage();
+  if (nf != 3 || (end != TSA_END_CORNER && !align)) return usage();
   uint8_t *s[3];
   int64_t n[3];
   for (int k = 0; k < 3; ++k) {
@@ -62,14 +72,25 @@ int main(int argc, char **argv) {
   if (align) {
     const int64_t cap = n[0] + n[1] + n[2];
     uint8_t *mv = (uint8_t *)malloc((size_t)cap);
-    int32_t nm = 0, st[3], sc = 0;
-    rc = mv ? tsa_align_gpu(s[0], (int32_t)n[0], s[1], (int32_t)n[1], s[2], (int32_t)n[2], &p, &sc,
-                            mv, (int32_t)cap, &nm, st, device)
-            : TSA_ENOMEM;
+    int32_t nm = 0, st[3], en[3], sc = 0;
+    if (!mv) rc = TSA_ENOMEM;
+    else if (end == TSA_END_CORNER)
+      rc = tsa_align_gpu(s[0], (int32_t)n[0], s[1], (int32_t)n[1], s[2], (int32_t)n[2], &p, &sc, mv, (int32_t)cap, &nm,
+                         st, device);
+    else {  // a batch of one: the three sequences back to back
+      uint8_t *seqs = (uint8_t *)malloc((size_t)cap);
+      const int64_t off[4] = {0, n[0], n[0] + n[1], cap};
+      if (seqs)
+        for (int k = 0; k < 3; ++k) memcpy(seqs + off[k], s[k], (size_t)n[k]);
+      rc = seqs ? tsa_align_batch_ends(seqs, off, 1, &p, end, &sc, mv, &nm, st, en, device) : TSA_ENOMEM;
+      free(seqs);
+    }
     if (rc) { fprintf(stderr, "tsa: %s (%d)\n", tsa_strerror(rc), rc); free(mv); return 1; }
     static const int use[7][3] = {{1, 1, 1}, {1, 0, 0}, {0, 1, 0}, {0, 0, 1}, {1, 1, 0}, {0, 1, 1}, {1, 0, 1}};
     static const char *letters = "ATCGN";
     printf("alignment start (x0,y0,z0) = (%d,%d,%d), %d columns\n", st[0], st[1], st[2], nm);
+    if (end != TSA_END_CORNER)
+      printf("alignment end (x1,y1,z1) = (%d,%d,%d), score %d\n", en[0], en[1], en[2], sc);
     for (int k = 0; k < 3; ++k) {
       int64_t pos = st[k];
       putchar("ABC"[k]);

@@ -316,6 +316,53 @@ int tsa_align_batch_grid(const uint8_t *seqs, const int64_t *offsets, int32_t n,
                          const tsa_params *p, int32_t *scores, uint8_t *moves,
                          int32_t *n_moves, int32_t *starts, int32_t device);
 
+/* End-free traceback: tsa_align_batch with a choice of where the path may end.
+ * The zero faces make the start of every alignment free; the reference takes
+ * FINAL_MAX at the corner (LA,LB,LC) alone (src/TriAlign_1cyc.v:141-142), so
+ * the entry points above all end there. end_mode selects the cells that may
+ * end the path:
+ *   TSA_END_CORNER  the cell (la,lb,lc): tsa_align_batch's result
+ *   TSA_END_FACE    real cells with x == la or y == lb or z == lc, where one
+ *                   sequence is used up (overlap alignment)
+ *   TSA_END_ANY     every real cell 1 <= x <= la, 1 <= y <= lb, 1 <= z <= lc
+ *                   (the best-scoring triple of prefixes)
+ * The end cell (x1,y1,z1) is the candidate whose MAX7 over its 7 states -- the
+ * literal wrapped values, compared as the final MAX7 compares them -- is
+ * largest; ties between cells go to the smallest x, then the smallest y, then
+ * the smallest z, ties between states to the lowest state index. The recurrence
+ * is causal, so that MAX7 is the score of the prefixes a[0..x1), b[0..y1),
+ * c[0..z1) and the path is their alignment, move for move. scores[i] is that
+ * MAX7, ends[3i..3i+2] = (x1,y1,z1); the path is walked from there, through
+ * the same pointer words, to the zero face it leaves, and starts, moves and
+ * n_moves (always >= 1) are as tsa_align_batch's: the alignment covers
+ * a[x0..x1), b[y0..y1), c[z0..z1), and the symbols beyond the end are no more
+ * aligned than those before the start.
+ *
+ * Layouts, validation order, error codes, thread safety, chunking under the
+ * pointer-cube budget and align_tb_bytes are tsa_align_batch's; also
+ * TSA_EINVAL for a null ends or an end_mode outside 0..2, before any device
+ * work. TSA_END_CORNER runs tsa_align_batch's own path, under every plan and
+ * override, and fills ends with the lengths. Under TSA_END_FACE and
+ * TSA_END_ANY a triple that fits one workgroup takes the resident kernel and
+ * every other one the tiled resident kernel, whatever their number (as under
+ * tsa_align_batch_async; tsa_describe_align_plan under align_mode = tiled
+ * describes the plan); align_tile holds, and a set align_mode of plane, strip
+ * or grid returns TSA_EINVAL. Both kernels search the end cell as they sweep,
+ * so capacity, tile geometry and budget needs are tsa_align_batch's, and a
+ * chunk queues its counted launches under align_mode = tiled:
+ * [resident] + [tiled].
+ *
+ * Not covered: the strip and grid paths, the plane sweep, tsa_align_gpu, a
+ * device-resident form (tsa_align_rows_async works on uploaded results as it
+ * is), and an end-free score-only mode of the helix and lap scorers. */
+#define TSA_END_CORNER 0
+#define TSA_END_FACE 1
+#define TSA_END_ANY 2
+int tsa_align_batch_ends(const uint8_t *seqs, const int64_t *offsets, int32_t n,
+                         const tsa_params *p, int32_t end_mode, int32_t *scores,
+                         uint8_t *moves, int32_t *n_moves, int32_t *starts,
+                         int32_t *ends, int32_t device);
+
 /* Device-resident traceback: tsa_align_batch on sequences that are already in
  * device memory, with results that stay there. d_* are device pointers on the
  * current device, stream is a hipStream_t (NULL = default stream). h_offsets

@@ -24,6 +24,14 @@ synchronous leg's do not. The form names the path of the larger triples
 (resident: no larger ones are expected, path tiled).
   python tools/align_bench.py --n 512 --la 64 --forms resident --async
   python tools/align_bench.py --n 256 --la 128 --forms tiled --async
+--end adds, for every batch form, a leg through tsa_align_batch_ends per listed
+end mode (<form>_end_<mode>_ms): corner runs tsa_align_batch's own path and
+must cost what the plain leg costs; face and any run the kernels that search
+the end cell as they sweep (resident and tiled only). Their results differ
+from the corner's by design, so only the corner leg joins the cross-check. A
+library without tsa_align_batch_ends (the parent of a comparison) skips them.
+  python tools/align_bench.py --n 512 --la 64 --forms resident --end corner,face,any
+  python tools/align_bench.py --n 256 --la 128 --forms tiled --end corner,face,any
 A library without tsa_align_batch (an older build named by TSA_PKG_DIR) runs
 the loop alone: that is how the baseline of a comparison is taken.
 Prints one JSON line: per form the median, min and max of the passes in ms."""
@@ -54,6 +62,7 @@ def main():
     ap.add_argument("--async", dest="async_", action="store_true",
                     help="add the tsa_align_batch_async leg of every batch form")
     ap.add_argument("--train", type=int, default=10, help="calls between the two events of an async pass")
+    ap.add_argument("--end", default="", help="comma list of end modes (corner, face, any): tsa_align_batch_ends legs")
     args = ap.parse_args()
     import bench
     tsa = bench.load_pkg()
@@ -77,6 +86,15 @@ def main():
                 ov["align_tb_bytes"] = args.tb_bytes
             with tsa.overrides(**ov):
                 return tsa.align_batch(seqs=seqs, offsets=offs)
+        return run
+
+    def batch_ends(mode, end):
+        def run():
+            ov = dict(align_mode=mode)
+            if args.tb_bytes is not None:
+                ov["align_tb_bytes"] = args.tb_bytes
+            with tsa.overrides(**ov):
+                return tsa.align_batch_ends(seqs=seqs, offsets=offs, end=end)
         return run
 
     def loop():
@@ -128,6 +146,9 @@ def main():
             forms[f] = batch(f)
             if args.async_ and f != "plane" and hasattr(tsa, "align_batch_async"):
                 forms[f + "_async"], timers[f + "_async"] = device_leg(f)
+            for e in filter(None, args.end.split(",")):
+                if hasattr(tsa, "align_batch_ends"):
+                    forms["%s_end_%s" % (f, e)] = batch_ends(f, e)
     out, refused = {}, {}
     for f, fn in list(forms.items()):                # first call: also the cross-check
         try:
@@ -135,7 +156,7 @@ def main():
         except tsa.TsaError as e:                    # e.g. TSA_ENOMEM: the form cannot run this batch
             refused[f] = str(e)
             del forms[f]
-    names = list(out)
+    names = [f for f in out if not f.endswith(("_end_face", "_end_any"))]
     same = True
     for f in names[1:]:
         for g, r in zip(out[f], out[names[0]]):

@@ -102,9 +102,11 @@ class Cell:
         return out
 
 
-def emulate(a, b, c, match=1, mismatch=-1, go=2, ge=1, sop=False, bits=12):
+def emulate(a, b, c, match=1, mismatch=-1, go=2, ge=1, sop=False, bits=12, on_cell=None):
     """(score, final7, ptr) by the resident schedule; ptr maps a cell
-    (x, y, z) to its pointer word."""
+    (x, y, z) to its pointer word. on_cell(x, y, z, states, p) is called for
+    every cell as the schedule computes it, p the number of its position in the
+    plane (tools/align_ends_emu.py folds the end keys there)."""
     K = Cell(a, b, c, match, mismatch, go, ge, sop, bits)
     la, lb, lc = K.la, K.lb, K.lc
     buf = [[[ZERO] * (lc + 1) for _ in range(lb + 1)] for _ in range(2)]
@@ -119,6 +121,8 @@ def emulate(a, b, c, match=1, mismatch=-1, go=2, ge=1, sop=False, bits=12):
             out = K.step(h, x, rd[y][z], rd[y - 1][z], rd[y][z - 1], rd[y - 1][z - 1], y, z)
             if out:
                 wr[y][z], ptr[(x, y, z)] = out
+                if on_cell:
+                    on_cell(x, y, z, out[0], (y - 1) * lc + (z - 1))
                 if (x, y, z) == (la, lb, lc):
                     fin = wr[y][z]
     return max(fin), fin, ptr
@@ -130,11 +134,17 @@ def walk(ptr, fin, la, lb, lc):
     for s in range(1, 7):
         if fin[s] > fin[T]:
             T = s
-    x, y, z, moves = la, lb, lc, []
+    return walk_from(ptr, T, la, lb, lc)
+
+
+def walk_from(ptr, T, x, y, z):
+    """((x0, y0, z0), moves in forward order) from cell (x, y, z) in state T:
+    walk_back of csrc/plane_kernel.hip, at most x + y + z moves."""
+    bound, moves = x + y + z, []
     while True:
         moves.append(T)
         px, py, pz = x - DX[T], y - DY[T], z - DZ[T]
-        if px == 0 or py == 0 or pz == 0 or len(moves) >= la + lb + lc:
+        if px == 0 or py == 0 or pz == 0 or len(moves) >= bound:
             x, y, z = px, py, pz
             break
         T = (ptr[(x, y, z)] >> (3 * T)) & 7

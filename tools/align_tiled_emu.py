@@ -42,9 +42,11 @@ def tile_geom(lb, lc, tymax, tzmax):
     return -(-lb // nty), -(-lc // ntz), nty, ntz
 
 
-def emulate(a, b, c, match=1, mismatch=-1, go=2, ge=1, sop=False, bits=12, tile=(64, 48)):
+def emulate(a, b, c, match=1, mismatch=-1, go=2, ge=1, sop=False, bits=12, tile=(64, 48), on_cell=None):
     """(score, final7, ptr) by the tiled schedule; ptr maps a cell (x, y, z)
-    in global coordinates to its pointer word."""
+    in global coordinates to its pointer word. on_cell(x, y, z, states, p) is
+    called for every cell as the schedule computes it, p the number of its
+    position in its tile (tools/align_ends_emu.py folds the end keys there)."""
     K = Cell(a, b, c, match, mismatch, go, ge, sop, bits)
     la, lb, lc = K.la, K.lb, K.lc
     TY, TZ, nty, ntz = tile_geom(lb, lc, *tile)
@@ -81,6 +83,8 @@ def emulate(a, b, c, match=1, mismatch=-1, go=2, ge=1, sop=False, bits=12, tile=
                     out = K.step(h, x, rd[y][z], rd[y - 1][z], rd[y][z - 1], rd[y - 1][z - 1], y0 + y, z0 + z)
                     if out:
                         new[(y, z)], ptr[(x, y0 + y, z0 + z)] = out
+                        if on_cell:
+                            on_cell(x, y0 + y, z0 + z, out[0], (y - 1) * tzl + (z - 1))
                         if (x, y0 + y, z0 + z) == (la, lb, lc):
                             fin = new[(y, z)]
                 for f in range(tzl + tyl + 1):                   # the face threads
