@@ -174,6 +174,31 @@ __device__ __forceinline__ void lds_w16_at(lds_u8 *base, int off, uint32_t v) {
 #ifndef TSA_RING_NT
 #define TSA_RING_NT 0
 #endif
+// V-space: wave 0 builds the y = 0 face records of its first lap from its own
+// H registers up to a switch step t_sw and fetches the ring only from there;
+// the prologue fills the dozen rows of steps [t_sw, lag) instead of the whole
+// ring (0: every row filled and fetched, 277 MB stored and 254 MB read back per
+// 512 x 256^3 launch for values that are formulas). Neutral on its own (1881-
+// 1898 against 1877-1898 GCUPS), +1.6 % once the barrier no longer waits for the
+// A read below: 1930-1947 against 1894-1922, eight interleaved bench passes
+// (profiles/r7_helix_ring_rows_ab.jsonl)
+#ifndef TSA_RING_FIRSTLAP
+#define TSA_RING_FIRSTLAP 1
+#endif
+// V-space: an even step reads the A codes of both steps after it, so the odd
+// step's barrier waits for its record writes alone (0: each step reads the
+// next one's, and every barrier's lgkmcnt(0) waits for that read's round trip);
+// +2.6 % (1937-1944 against 1881-1898 GCUPS, four passes, r7)
+#ifndef TSA_A_EVEN_READS
+#define TSA_A_EVEN_READS 1
+#endif
+// V-space: the record slots' and the A table's per-lane addresses held in
+// VGPRs (0: the compiler re-adds the lane's part to an SGPR base in every
+// four-step group, 2 VALU of 268; +0.4 % on average, 1937-1955 against 1937-
+// 1944 GCUPS, not resolved pass by pass, r7)
+#ifndef TSA_PIN_BASES
+#define TSA_PIN_BASES 1
+#endif
 // wave 0's per-step fetch of an M = 2 ring row as one statement: both 1 KiB
 // pieces through the saddr form (the row's SGPR base, the lane's two constant
 // VGPR offsets), M0 set from a 32-bit LDS address -- no per-step 64-bit VALU
@@ -434,6 +459,9 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
   // below (LDS pointers, so the slot offsets fold into the ds instructions)
   const lds_u8 *rd_base = to_lds(xr + (w > 0 ? (w - 1) * HNSL * SLOT_BYTES : 0) + lane * REC_BYTES);
   lds_u8 *wr_base = to_lds(xr + w * HNSL * SLOT_BYTES + lane * REC_BYTES);
+  // TSA_PIN_BASES: both held in VGPRs (left alone, the compiler keeps the wave's
+  // part in an SGPR and adds the lane's part again in every four-step group)
+  if constexpr (VS && !SHR && TSA_PIN_BASES) asm volatile("" : "+v"(rd_base), "+v"(wr_base));
   // SHR (TSA_SHIFTED_REC): the writes of a shifted record. Register M-1's
   // {Iyz, best} go to lane + 1's pair 0 (lanes 0..62); lane 0's pair-0
   // {Iyz, best} take lane 63's register M-1 low halves in their high halves
@@ -483,13 +511,29 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
     }
     // ring rows of wave 0's lap 0 -> ring row (t - lag) mod R at step t
     const int32_t lag = P - HSK * (NW - 1);
-    {
+    // FIRSTLAP: wave 0 builds the face records of its steps [0, t_sw) from its own
+    // H registers (first-lap role, ROLE 3 in step) and fetches the ring from step
+    // t_sw on, a whole group at least PD steps before the last wave's first row
+    // (step lag). Only the rows of steps [t_sw, lag) are filled here: every
+    // other row wave 0 fetches was written by the last wave of this unit, so a
+    // workspace may hold anything (an earlier unit's or launch's rows) at entry
+    constexpr bool FIRSTLAP = VS && TSA_RING_FIRSTLAP;
+    const int32_t t_sw = FIRSTLAP ? max(lag - PD, 0) & ~3 : 0;
+    if constexpr (FIRSTLAP) {
+      // row 0's face cells as wave 0 meets them at step tr: x + z = tr + 2 for
+      // every position ({Iy, Ixy, Iyz, best} = lam q - lam, lam q x 3); step tr
+      // < lag reads ring row (tr - lag) mod R = R - lag + tr
+      const int32_t n16 = (lag - t_sw) * M * 64;
+      for (int32_t i = threadIdx.x; i < n16; i += 64 * NW) {
+        const int32_t tr = t_sw + i / (M * 64);
+        const uint32_t f1 = h_bits(pa.lam * (tr + 1)), f2 = h_bits(pa.lam * (tr + 2));
+        ((uint4 *)ring)[(int64_t)(R - lag + tr) * (M * 64) + i % (M * 64)] = make_uint4(f1, f2, f2, f2);
+      }
+    } else {
       const uint4 face = make_uint4(pa.f_single, pa.f_pair, pa.f_pair, 0u);
       const int64_t n16 = (int64_t)R * M * 64;
       for (int64_t i = threadIdx.x; i < n16; i += 64 * NW) {
-        if constexpr (VS) {
-          // row 0's face cells as wave 0 meets them at step tr: x + z = tr + 2 for
-          // every position ({Iy, Ixy, Iyz, best} = lam q - lam, lam q x 3)
+        if constexpr (VS) {  // every row (TSA_RING_FIRSTLAP=0): ring row r is the row of step (r + lag) mod R
           const int32_t tr = (int32_t)((i / (M * 64) + lag) % R);
           const uint32_t f1 = h_bits(pa.lam * (tr + 1)), f2 = h_bits(pa.lam * (tr + 2));
           ((uint4 *)ring)[i] = make_uint4(f1, f2, f2, f2);
@@ -611,23 +655,33 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
         s0[3 * SLOT_BYTES / 4] = s0[3 * SLOT_BYTES / 4 + 1] = f2;
       }
     }
-    // wave 0: prime the LDS-DMA pipeline (ring row of step s = s - P + NW - 1)
-    if (w == 0) {
+    // wave 0: prime the LDS-DMA pipeline with the rows of steps t0 .. t0 + PD - 1
+    // (ring row of step s = s - lag) before its first fetching step t0 (VS: t_sw)
+    int32_t dma_row = 0;  // ring row for step t + PD
+    auto prime = [&](int32_t t0) {
 #pragma unroll 1
-      for (int s = 0; s < PD; ++s) {
+      for (int s = t0; s < t0 + PD; ++s) {
         const int32_t row = ((s - lag) % R + R) % R;
 #pragma unroll
         for (int i = 0; i < M; ++i)
           dma16(ring + ((int64_t)row * M + i) * PAIR_BYTES + lane * REC_BYTES,
                 xr0 + (s % PD) * SLOT_BYTES + i * PAIR_BYTES);
       }
+      dma_row = ((t0 + PD - lag) % R + R) % R;
+    };
+    if constexpr (!FIRSTLAP) {
+      if (w == 0) prime(0);
     }
-    int32_t dma_row = ((PD - lag) % R + R) % R;  // ring row for step t + PD
     const uint32_t dvo0 = (uint32_t)lane * REC_BYTES, dvo1 = dvo0 + PAIR_BYTES;  // TSA_DMA_SADDR
     const uint32_t xr0_lds = __builtin_amdgcn_readfirstlane(
         (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)xr0);
-    uint32_t a_nx[M];                            // A codes of the coming step
-    if constexpr (TSA_A_PREFETCH) load_a<M>(a_lane + 4u * (uint32_t)xpos0, a_nx);
+    uint32_t a_nx[M];                            // A codes of the coming step (A_EVEN: the coming odd step)
+    // A_EVEN: the coming even step's. An even step reads the codes of both steps
+    // after it, so no LDS read is pending at the barrier that ends the odd one
+    constexpr bool A_EVEN = VS && TSA_A_EVEN_READS && TSA_A_PREFETCH;
+    uint32_t a_ev[M];
+    if constexpr (A_EVEN) load_a<M>(a_lane + 4u * (uint32_t)xpos0, a_ev);
+    else if constexpr (TSA_A_PREFETCH) load_a<M>(a_lane + 4u * (uint32_t)xpos0, a_nx);
     int32_t st_row = 0;                          // ring row written at step t (last wave)
     uint32_t abase = a_lane;                     // VS: A address of the group's first step
     // A_B64: the same entry in the shifted copy
@@ -695,7 +749,7 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
       uint32_t a[M];
       if constexpr (TSA_A_PREFETCH) {
 #pragma unroll
-        for (int i = 0; i < M; ++i) a[i] = a_nx[i];
+        for (int i = 0; i < M; ++i) a[i] = (A_EVEN && PH == 0) ? a_ev[i] : a_nx[i];
       } else {
         load_a<M>(a_lane + 4u * (uint32_t)xpos0, a);
       }
@@ -706,6 +760,14 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
         const uint8_t *src = xr0 + (t % PD) * SLOT_BYTES + lane * REC_BYTES;
 #pragma unroll
         for (int i = 0; i < M; ++i) rec[i] = lds_read16(src + i * PAIR_BYTES);
+      } else if constexpr (ROLE == 3) {
+        // wave 0 before step t_sw: row 0's face record, x + z = t + 2 at every
+        // position -- {lam (t + 1), lam (t + 2) x 3} = {H(t), H(t + 1) x 3} of
+        // this wave (y = 1, xpos0 = t: no wrap before step P > t_sw)
+        static_assert(ROLE != 3 || VS, "the first-lap role reads the V-space H registers");
+#pragma unroll
+        for (int i = 0; i < M; ++i)
+          rec[i] = make_uint4(Hr[PQ & 3], Hr[(PQ + 1) & 3], Hr[(PQ + 1) & 3], Hr[(PQ + 1) & 3]);
       } else {
         const int off = (HSK == 2 ? (q + 2) & 3 : PH ^ 1) * SLOT_BYTES;
 #pragma unroll
@@ -1008,9 +1070,24 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
         zshift<M>(svM[PH], rw, sel, 0u);
         advance();
       }
-      if constexpr (A_B64) load_a_pair<(PQ & 3) + 1>(abase, abase_s, a_nx);  // x' of step t + 1
-      else if constexpr (VS) load_a_off<M>(abase, (PQ & 3) + 1, a_nx);
-      else if constexpr (TSA_A_PREFETCH) load_a<M>(a_lane + 4u * (uint32_t)xpos0, a_nx);
+      if constexpr (VS && !A_EVEN) {  // x' of step t + 1
+        if constexpr (A_B64) load_a_pair<(PQ & 3) + 1>(abase, abase_s, a_nx);
+        else load_a_off<M>(abase, (PQ & 3) + 1, a_nx);
+      } else if constexpr (VS) {
+        // x' of steps t + 1 and t + 2, both read in the even step: the odd step
+        // ends at the barrier, which then waits for its record writes alone
+        if constexpr (PH == 0) {
+          if constexpr (A_B64) {
+            load_a_pair<(PQ & 3) + 1>(abase, abase_s, a_nx);
+            load_a_pair<(PQ & 3) + 2>(abase, abase_s, a_ev);
+          } else {
+            load_a_off<M>(abase, (PQ & 3) + 1, a_nx);
+            load_a_off<M>(abase, (PQ & 3) + 2, a_ev);
+          }
+        }
+      } else if constexpr (TSA_A_PREFETCH) {
+        load_a<M>(a_lane + 4u * (uint32_t)xpos0, a_nx);
+      }
 
       // ---- wave 0: fetch the record of step t + PD into the slot just consumed
       if constexpr (ROLE == 0 && TSA_ABL_RING != 1 && TSA_ABL_RING != 3) {
@@ -1059,10 +1136,27 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
         // SHR: lane 63's write base in a VGPR (uniform, the compiler would keep it
         // in an SGPR and copy it into a VGPR before every write)
         if constexpr (SHR) asm volatile("" : "+v"(wrH));
-#pragma unroll 1
-        for (; t < T; t += 4) {
+        auto group_bases = [&]() {  // the A addresses of the group's first step
           abase = a_lane + 4u * (uint32_t)xpos0;
           if constexpr (A_B64) abase_s = a_lane_s + 4u * (uint32_t)xpos0;
+        };
+        if constexpr (FIRSTLAP && (decltype(role)::value & 3) == 0) {
+          // wave 0's first lap: whole groups in the first-lap role (no fetch, no
+          // vmcnt wait) up to step t_sw, then the fetch pipeline and ROLE 0
+          constexpr std::integral_constant<int, decltype(role)::value | 3> first{};
+#pragma unroll 1
+          for (; t < t_sw && t < T; t += 4) {
+            group_bases();
+            TSA_INLINE_IF_WIDE(step(Q0, first, t, mid));
+            TSA_INLINE_IF_WIDE(step(Q1, first, t + 1, mid));
+            TSA_INLINE_IF_WIDE(step(Q2, first, t + 2, mid));
+            TSA_INLINE_IF_WIDE(step(Q3, first, t + 3, mid));
+          }
+          if (t < T) prime(t);
+        }
+#pragma unroll 1
+        for (; t < T; t += 4) {
+          group_bases();
           TSA_INLINE_IF_WIDE(step(Q0, role, t, mid));
           TSA_INLINE_IF_WIDE(step(Q1, role, t + 1, mid));
           TSA_INLINE_IF_WIDE(step(Q2, role, t + 2, mid));

@@ -8,6 +8,11 @@ the message form (`vs=False`) or the V-space form of cell_messages_vs
 (`vs=True`: values shifted by lam*(x+y+z), faces lam*q). tests/
 test_pencil_schedule.py checks it against the oracle.
 
+V-space replays the kernel's first-lap role too: wave 0 builds the y = 0 face
+records of its steps before t_sw from its own H values, only the ring rows of
+steps [t_sw, lag) are filled, and `ring_garbage_seed` starts the ring as
+garbage, so a row read before it is written shows (tests/test_helix_ring_emu.py).
+
 `shifted=True` (V-space only; the kernel's TSA_SHIFTED_REC) replays the
 writer-side record shift: a wave (and the last wave, into the ring) stores
 each position's {Iyz, best} at position k+1, lane 0's low halves carrying the
@@ -24,7 +29,8 @@ from __future__ import annotations
 
 import numpy as np
 
-NW, S, RING_EXTRA = 8, 2, 8
+NW, S, RING_EXTRA, PD = 8, 2, 8, 8
+FILL_FROM = 0  # test hook: the first rows wave 0 fetches left unfilled (the garbage ring must then show)
 
 
 def penalties(go, ge):
@@ -38,9 +44,13 @@ def penalties(go, ge):
                      [go, ge, go, ge, go, go, ge]], dtype=np.int64)
 
 
-def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shifted=None, garbage_seed=None):
+def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shifted=None, garbage_seed=None,
+            ring_garbage_seed=None):
     """Scores of one workgroup's unit: one triple, or two (TWO mode: LC <= 64).
-    Returns a list of scores (one per triple)."""
+    Returns a list of scores (one per triple). `garbage_seed` starts the LDS
+    record slots, `ring_garbage_seed` the global ring, with garbage (what an
+    earlier launch left in the workspace): a ring row read before this unit
+    wrote it then spoils the score."""
     two = len(triples) == 2
     shifted = vs if shifted is None else shifted
     assert vs or not shifted
@@ -96,8 +106,16 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
             return np.array([lam * (tr + 1), lam * (tr + 2), lam * (tr + 2), lam * (tr + 2)])
         return np.array([f_single, f_pair, f_pair, 0])
 
-    ring = np.stack([face_rec((r + lag) % R)[:, None, None, None] * np.ones((1,) + shape, np.int64)
-                     for r in range(R)])          # [R, 4, M, 64, 2]
+    # V-space: wave 0 builds the face records of its steps [0, t_sw) from its own
+    # H values (the kernel's first-lap role) and reads the ring from step t_sw,
+    # a whole group at least PD steps before the last wave's first row; only the
+    # rows of steps [t_sw, lag) are filled. The message form fills every row.
+    t_sw = (max(lag - PD, 0) & ~3) if vs else 0
+    ring = np.zeros((R, 4) + shape, np.int64)     # [R, 4, M, 64, 2]
+    if ring_garbage_seed is not None:
+        ring = np.random.default_rng(ring_garbage_seed).integers(-3000, 3000, ring.shape)
+    for tr in (range(t_sw + FILL_FROM, lag) if vs else range(lag, lag + R)):
+        ring[(tr - lag) % R] = face_rec(tr % R)[:, None, None, None] * np.ones((1,) + shape, np.int64)
     xr = np.zeros((NW, 4, 4) + shape, np.int64)    # [wave][slot][field]
     if garbage_seed is not None:  # LDS starts with whatever the last kernel left
         xr = np.random.default_rng(garbage_seed).integers(-3000, 3000, xr.shape)
@@ -142,7 +160,11 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
         outs = [None] * NW
         for w in range(NW):
             d = st[w]
-            rec = ring[(t - lag) % R] if w == 0 else xr[w - 1, (t - S) & 3]
+            if w == 0 and t < t_sw:  # {H(t), H(t + 1) x 3} in every position
+                rec = np.array([d["H"][t], d["H"][t + 1], d["H"][t + 1], d["H"][t + 1]])[:, None, None, None] * \
+                    np.ones((1,) + shape, np.int64)
+            else:
+                rec = ring[(t - lag) % R] if w == 0 else xr[w - 1, (t - S) & 3]
             u = (t - S * w - kpos) % P
             acode = per_half(lambda tr, h: code(tr[0], u))
             inIx, inIy, inIz = d["oIx"].copy(), rec[0].copy(), d["shIz"].copy()
