@@ -191,6 +191,11 @@ __device__ __forceinline__ uint4 lds_read16_at(const lds_u8 *base, int off) {
   const u32x4_lds v = *(const __attribute__((address_space(3))) u32x4_lds *)(base + off);
   return make_uint4(v.x, v.y, v.z, v.w);
 }
+// 8 bytes of a record as one ds_read_b64
+__device__ __forceinline__ uint2 lds_read8_at(const lds_u8 *base, int off) {
+  const uint64_t v = *(const __attribute__((address_space(3))) uint64_t *)(base + off);
+  return make_uint2((uint32_t)v, (uint32_t)(v >> 32));
+}
 __device__ __forceinline__ void lds_write16_at(lds_u8 *base, int off, uint4 v) {
   *(__attribute__((address_space(3))) u32x4_lds *)(base + off) = (u32x4_lds){v.x, v.y, v.z, v.w};
 }
@@ -440,6 +445,15 @@ __device__ __forceinline__ void zshift(uint32_t (&v)[M], const uint32_t (&src)[M
 #pragma unroll
   for (int i = M - 1; i >= 1; --i) v[i] = src[i - 1];
   v[0] = __builtin_amdgcn_perm(r, face, sel);
+}
+// The same for values read at position k-1 already (the reader aimed its LDS
+// read at the previous position's record): only lane 0's register 0 changes,
+// {face, lane 63's low half}; the v_perm passes every other lane's through.
+template <int M>
+__device__ __forceinline__ void zfix(uint32_t (&v)[M], const uint32_t (&src)[M], uint32_t sel, uint32_t face) {
+#pragma unroll
+  for (int i = M - 1; i >= 1; --i) v[i] = src[i];
+  v[0] = __builtin_amdgcn_perm(src[0], face, sel);
 }
 // A codes of a lane's M registers: entries va, va-4, ... of the LDS table
 // (register i holds position M*lane+i, one x behind register i-1).

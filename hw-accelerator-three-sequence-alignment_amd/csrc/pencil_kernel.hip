@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "pencil_common.h"
+#include "h_table.h"
 #include "lap_kernel.h"
 
 namespace tsa {
@@ -70,45 +71,47 @@ constexpr int RING_EXTRA = 8;
 #ifndef TSA_EV_STATIC
 #define TSA_EV_STATIC 1
 #endif
-// V-space: the face values H(s) = lam q kept as wave-uniform integers and
-// encoded to f16 bits in SALU (f16x2_int), so they live in SGPRs: no VALU add
-// per step, and the bfi / perm that inject them read the SGPR directly
-#ifndef TSA_H_SALU  // (measured slower: 1667 / 1645 vs 1697 / 1687 GCUPS, profiles/r5b_helix_ab.jsonl)
-#define TSA_H_SALU 0
+// V-space M = 2: the face values H(s) = lam q live in SGPRs, read from a
+// constant table of f16 bits (h_table.h) by scalar loads: no VALU add per
+// step, and the bfi / perm that inject them read the SGPR directly. A wave
+// keeps the integer lam q; each four-step group fetches the next group's four
+// values (one four-dword load for lam = 1, where they are contiguous, else one
+// load per value) at the top of its third step, and the fourth step's
+// `s_waitcnt lgkmcnt(0)` before the barrier covers them. At a lap wrap the
+// restarted values come from the same table, waited for in place (once per
+// lap). 0: one v_pk_add_f16 per step on VGPR copies. Parity-green, 8 VALU per
+// group fewer (266 -> 260 with it alone) and measured SLOWER, so off: 1872-1902
+// against 1907-1921 GCUPS, four interleaved bench passes on one box
+// (profiles/r8_helix_ab.jsonl) -- with a scalar load in flight every LDS wait
+// of the step that issues it is an lgkmcnt(0). (An earlier SGPR form encoded
+// each value in SALU, 11 instructions per step, and measured slower too:
+// 1667 / 1645 vs 1697 / 1687 GCUPS, profiles/r5b_helix_ab.jsonl.)
+#ifndef TSA_H_TAB
+#define TSA_H_TAB 0
 #endif
 // V-space: step s's x = 1 injection applied to the state registers at the end
 // of step s - 1 (before the step barrier), not to the inputs at the start of
 // step s, where it stood between the barrier and the cell
-#ifndef TSA_PREINJ  // (measured neutral with TSA_H_SALU: 1646 / 1646 vs 1667 / 1645, r5b)
+#ifndef TSA_PREINJ  // (measured neutral with the SALU-encoded H: 1646 / 1646 vs 1667 / 1645, r5b)
 #define TSA_PREINJ 0
 #endif
-// f16 bits of the integer v in both halves, exact for 0 <= v <= 2047 --
-// integer ops only, so a wave-uniform v stays in SALU (~8 instructions). The
-// face values lam q are >= 0, and < 2048 at every real cell (use_vs); a
-// padding position (x > LA) may see a larger q, clamped to a finite value
-// (its cells feed only padding cells and the x = 1 inputs the bfi replaces).
-// With c = clz(v), v << (c - 21) puts the leading 1 at bit 10, which adds the
-// one missing from the exponent field (45 - c - 1) + 1 = e + 15.
-// Written in SALU asm: left to itself the compiler picks v_med3_i32 for the
-// clamp and then keeps the whole encode in VALU (v is wave-uniform).
-__device__ __forceinline__ uint32_t f16x2_int(int32_t v) {
-  uint32_t r, a, c, t;
-  asm("s_min_u32 %1, %4, 0x7ff\n\t"       // a = min(v, 2047) (v >= 0; unsigned: a negative v clamps too)
-      "s_or_b32 %2, %1, 1\n\t"
-      "s_flbit_i32_b32 %2, %2\n\t"         // c = clz(a | 1), 21..31
-      "s_sub_u32 %3, %2, 21\n\t"
-      "s_lshl_b32 %3, %1, %3\n\t"          // a << (c - 21): the leading 1 at bit 10
-      "s_sub_u32 %2, 45, %2\n\t"
-      "s_lshl_b32 %2, %2, 10\n\t"
-      "s_add_u32 %3, %3, %2\n\t"           // + (45 - c) << 10
-      "s_cmp_eq_u32 %1, 0\n\t"
-      "s_cselect_b32 %3, 0, %3\n\t"
-      "s_pack_ll_b32_b16 %0, %3, %3"
-      : "=s"(r), "=&s"(a), "=&s"(c), "=&s"(t)
-      : "s"(v)
-      : "scc");
-  return r;
-}
+// V-space M = 2: a reader takes {Iyz, best} of the row above from the record of
+// position k - 1 -- register i - 1 of its own lane, or register M - 1 of lane
+// - 1 (lane 63 for lane 0) for register 0 -- by the address of its LDS read,
+// not from its own record through a DPP wave_ror:1. Lane 0's v_perm stays (the
+// z = 0 face in the low half, lane 63's low half in the high half); no record
+// write, ring store or ring fill changes. 0: own record, DPP + v_perm. 8 VALU
+// per group fewer (266 -> 258); 1932-1951 against 1907-1921 GCUPS, every pass
+// above every pass of the parent (profiles/r8_helix_ab.jsonl)
+#ifndef TSA_REC_PREV
+#define TSA_REC_PREV 1
+#endif
+// (The last wave's ring records as buffer stores -- the ring an SGPR resource,
+// the row in the scalar offset, the lane's place a loop-invariant VGPR, no
+// 64-bit VALU address per store -- were built in round 8, brought the last
+// wave's group to the middle waves' VALU count, and measured 12 % slower:
+// 1652-1658 against 1875-1890 GCUPS, profiles/r8_helix_ab.jsonl. Not kept;
+// DESIGN.md 4.2 describes the form.)
 // v_bfi_b32 with an SGPR source for the selected bits
 __device__ __forceinline__ uint32_t vbfi_s(uint32_t mask, uint32_t a, uint32_t b) {
   uint32_t r;
@@ -457,11 +460,23 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
 
   // this lane's record slots: read from the wave above, written for the one
   // below (LDS pointers, so the slot offsets fold into the ds instructions)
-  const lds_u8 *rd_base = to_lds(xr + (w > 0 ? (w - 1) * HNSL * SLOT_BYTES : 0) + lane * REC_BYTES);
+  // (wave 0 reads the ring rows prefetched into xr0, slot by slot)
+  uint8_t *rd_wave = w > 0 ? xr + (w - 1) * HNSL * SLOT_BYTES : xr0;
+  const lds_u8 *rd_base = to_lds(rd_wave + lane * REC_BYTES);
   lds_u8 *wr_base = to_lds(xr + w * HNSL * SLOT_BYTES + lane * REC_BYTES);
-  // TSA_PIN_BASES: both held in VGPRs (left alone, the compiler keeps the wave's
+  // RP (TSA_REC_PREV): the record of the previous position's last register,
+  // lane - 1's (lane 63's for lane 0), where a lane reads register 0's {Iyz, best}
+  constexpr bool RP = VS && M == 2 && !TWO && HSK == 2 && TSA_REC_PREV && !SHR && !TSA_ABL_ZREC;
+  const lds_u8 *rd_prev = to_lds(rd_wave + ((lane + 63) & 63) * REC_BYTES);
+  // TSA_PIN_BASES: all held in VGPRs (left alone, the compiler keeps the wave's
   // part in an SGPR and adds the lane's part again in every four-step group)
   if constexpr (VS && !SHR && TSA_PIN_BASES) asm volatile("" : "+v"(rd_base), "+v"(wr_base));
+  if constexpr (RP && TSA_PIN_BASES) asm volatile("" : "+v"(rd_prev));
+  // HT (TSA_H_TAB): H in SGPRs, from the constant table (a function-local
+  // constant: a private object at a pc-relative address, where a __constant__
+  // variable is visible to the host and reached through a loaded address)
+  static constexpr HTable H_TABLE = make_h_table();
+  constexpr bool HT = VS && M == 2 && !TWO && HSK == 2 && TSA_H_TAB && TSA_EV_STATIC && TSA_HM_TRACK;
   // SHR (TSA_SHIFTED_REC): the writes of a shifted record. Register M-1's
   // {Iyz, best} go to lane + 1's pair 0 (lanes 0..62); lane 0's pair-0
   // {Iyz, best} take lane 63's register M-1 low halves in their high halves
@@ -616,24 +631,54 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
 
     // VS: Hr[s & 3] = H(s) = lam * (y + xpos0) at step s (y: position 0's row,
     // 1-based) -- the x = 0 face at the x = 1 position and, one and two steps
-    // ahead, the z = 0 face of position 0; one v_pk_add per step, reset at a wrap
+    // ahead, the z = 0 face of position 0; step s sets H(s + 2): one v_pk_add,
+    // or (HT) the table's entry, reset at a wrap
     uint32_t Hr[4] = {0u, 0u, 0u, 0u};
-    int32_t Hq[4] = {0, 0, 0, 0};  // TSA_H_SALU: lam q as integers (Hr = their f16 bits)
     auto hq_at = [&](int32_t s) -> int32_t {
       const int32_t u = s - HSK * w;
       const int32_t lp = u >= 0 ? u / P : -((P - 1 - u) / P);
       return pa.lam * (lp * NW + w + 1 + (u - lp * P));
     };
-    auto h_at = [&](int32_t s) -> uint32_t { return TSA_H_SALU ? f16x2_int(hq_at(s)) : h_bits(hq_at(s)); };
+    // HT: the table's entry of lam q (wave-uniform: a scalar load); the unsigned
+    // clamp keeps any q, a padding position's or a negative one, inside the table
+    auto h_tab = [&](int32_t q) -> uint32_t {
+      return H_TABLE.v[min((uint32_t)q, (uint32_t)H_TAB_SAT)];
+    };
+    // four values lam q0, lam q0 + lam, ...: contiguous entries for lam = 1 (the
+    // RTL's constants), read as one four-dword load -- a scalar load's address
+    // needs dword alignment only, whatever its width; an index clamped to
+    // H_TAB_SAT + 1 reads the saturated tail (H_TAB_N). l1: lam = 1 is known
+    // at compile time (the loop's lam = 1 version, see run below): a run-time
+    // test here would merge the two forms' registers right after the loads,
+    // and the copies would wait for them
+    auto h_tab4 = [&](auto l1, int32_t q0, uint32_t (&out)[4]) {
+      if constexpr (decltype(l1)::value) {
+        typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+        const u32x4_a4 v = *(const u32x4_a4 *)&H_TABLE.v[min((uint32_t)q0, (uint32_t)H_TAB_SAT + 1u)];
+        out[0] = v.x, out[1] = v.y, out[2] = v.z, out[3] = v.w;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) out[j] = h_tab(q0 + j * pa.lam);
+      }
+    };
+    // HT: hg = lam q of the H the group's last step sets (no wrap: + 4 lam per
+    // group); Hn the four values the group's steps set, Hp the next group's
+    int32_t hg = 0;
+    uint32_t Hn[4] = {0u, 0u, 0u, 0u}, Hp[4] = {0u, 0u, 0u, 0u};
     if constexpr (VS) {
-      Hq[0] = hq_at(0);
-      Hq[1] = hq_at(1);
-      Hq[3] = Hq[0] - pa.lam;
-      Hr[0] = h_at(0);
-      Hr[1] = h_at(1);
       // the step-0 injection's (0, y-1, z-1) face is H(0) - lam (wave 0 starts
       // its first row at step 0 with no wrap that would have set it)
-      Hr[3] = TSA_H_SALU ? f16x2_int(Hq[3]) : U(H(Hr[0]) - H(pa.v_lam));
+      if constexpr (HT) {
+        Hr[0] = h_tab(hq_at(0));
+        Hr[1] = h_tab(hq_at(1));
+        Hr[3] = h_tab(hq_at(0) - pa.lam);
+        hg = hq_at(1);  // the first group adds its 4 lam (group_bases)
+        h_tab4(std::false_type{}, hg + pa.lam, Hp);
+      } else {
+        Hr[0] = h_bits(hq_at(0));
+        Hr[1] = h_bits(hq_at(1));
+        Hr[3] = U(H(Hr[0]) - H(pa.v_lam));
+      }
       if (w == 0) {  // position 0's z = 0 faces at steps 0 and 1 (as if shifted in at steps -1, -2)
 #pragma unroll
         for (int i = 0; i < M; ++i) {
@@ -687,6 +732,7 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
     // A_B64: the same entry in the shifted copy
     const uint32_t a_lane_s = a_lane + (uint32_t)((uint8_t *)sA2s - (uint8_t *)sA2);
     uint32_t abase_s = a_lane_s;
+    const lds_u8 *r0_own = rd_base, *r0_prev = rd_prev;  // RP, wave 0: the group's four xr0 slots
 
     // VS: the step whose cell is the final one, in this wave (-1: none)
     const int32_t t_fin = w == w_f ? T - 1 : -1;
@@ -713,7 +759,7 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
 #pragma unroll
       for (int i = 0; i < M; ++i) {
         if (ISN >= 0 ? i == ISN : i == is) {
-          if constexpr (TSA_H_SALU) {
+          if constexpr (HT) {
             oIx[i] = vbfi_s(m1, Hr[PQN & 3], oIx[i]);
             svIxy[i] = vbfi_s(m1, Hr[PQN & 3], svIxy[i]);
             shIxz[PHN][i] = vbfi_s(m1, Hr[PQN & 3], shIxz[PHN][i]);
@@ -742,7 +788,8 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
       constexpr int ROLE = decltype(role)::value & 3;
       // M = 2 with even P: the x = 1 position's register (t - w) mod 2 is
       // PH ^ (w & 1), a compile-time constant for a wave of known parity
-      constexpr int WPAR = (decltype(role)::value >> 2) - 1;  // -1: unknown
+      constexpr int WPAR = ((decltype(role)::value >> 2) & 3) - 1;  // -1: unknown
+      constexpr bool L1 = (decltype(role)::value >> 4) & 1;  // HT: the loop's lam = 1 version
       constexpr int ISC = (M == 2 && WPAR >= 0) ? (HSK == 2 ? PH : PH ^ WPAR) : -1;
       constexpr bool FIN = decltype(fin_step)::value;  // the last step (t == T-1)
       // this step's A codes (LDS table) and the B code of position x = 1
@@ -753,9 +800,31 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
       } else {
         load_a<M>(a_lane + 4u * (uint32_t)xpos0, a);
       }
+      // HT: the next group's four H values, fetched at the top of the group's
+      // third step: the scalar loads return with this step's record reads, and
+      // the next step's lgkmcnt(0) before its barrier covers them in any case
+      if constexpr (HT && PQ == 2) h_tab4(std::bool_constant<L1>{}, hg + pa.lam, Hp);
       // ---- receive the wave-above record of step t-1
+      // RP: {Iy, Ixy} of the lane's own record, {Iyz, best} of position k - 1's
+      // (rec[i].z / .w then hold the values already shifted, but for lane 0's
+      // fix). Register 0 of the own record comes whole: its {Iyz, best} are
+      // register 1's; register 0's are lane - 1's register M - 1
       uint4 rec[M];
-      if constexpr (ROLE == 0) {
+      [[maybe_unused]] auto read_prev = [&](const lds_u8 *own_b, const lds_u8 *prev_b, int off) {
+        static_assert(!RP || M == 2, "TSA_REC_PREV: the M = 2 helix");
+        const uint4 r0 = lds_read16_at(own_b, off);
+        const uint2 r1 = lds_read8_at(own_b, off + PAIR_BYTES);
+        const uint2 rp = lds_read8_at(prev_b, off + (M - 1) * PAIR_BYTES + 8);
+        rec[0] = make_uint4(r0.x, r0.y, rp.x, rp.y);
+        rec[M - 1] = make_uint4(r1.x, r1.y, r0.z, r0.w);
+      };
+      if constexpr (ROLE == 0 && RP) {
+        // the slot of step t is (t % PD): r0_own / r0_prev hold the group's part
+        // (PD = 8, two groups), the step's is a constant offset
+        static_assert(!RP || PD == 8, "TSA_REC_PREV: wave 0's slots as two groups of four");
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(M * (PD - 1)) : "memory");
+        read_prev(r0_own, r0_prev, (PQ & 3) * SLOT_BYTES);
+      } else if constexpr (ROLE == 0) {
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(M * (PD - 1)) : "memory");
         const uint8_t *src = xr0 + (t % PD) * SLOT_BYTES + lane * REC_BYTES;
 #pragma unroll
@@ -770,8 +839,12 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
           rec[i] = make_uint4(Hr[PQ & 3], Hr[(PQ + 1) & 3], Hr[(PQ + 1) & 3], Hr[(PQ + 1) & 3]);
       } else {
         const int off = (HSK == 2 ? (q + 2) & 3 : PH ^ 1) * SLOT_BYTES;
+        if constexpr (RP) {
+          read_prev(rd_base, rd_prev, off);
+        } else {
 #pragma unroll
-        for (int i = 0; i < M; ++i) rec[i] = lds_read16_at(rd_base, off + i * PAIR_BYTES);
+          for (int i = 0; i < M; ++i) rec[i] = lds_read16_at(rd_base, off + i * PAIR_BYTES);
+        }
       }
       uint32_t inIx[M], inIy[M], inIz[M], inIxy[M], inIyz[M], inIxz[M], inM[M];
 #pragma unroll
@@ -811,7 +884,7 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
         for (int i = 0; i < M; ++i) {
           if (ISC >= 0 ? i == ISC : i == is) {
             if constexpr (VS) {  // faces (0,y,z), (0,y-1,z), (0,y,z-1): lam(y+z-1); (0,y-1,z-1): one lam less
-              if constexpr (TSA_H_SALU) {
+              if constexpr (HT) {
                 inIx[i] = vbfi_s(m1, Hr[PQ & 3], inIx[i]);
                 inIxy[i] = vbfi_s(m1, Hr[PQ & 3], inIxy[i]);
                 inIxz[i] = vbfi_s(m1, Hr[PQ & 3], inIxz[i]);
@@ -982,13 +1055,16 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
             row_terms();
             if constexpr (VS) {  // a new row at position 0: H(t .. t+2) restart
               const int32_t y = lap0 * NW + w + 1;
-              if constexpr (TSA_H_SALU) {
-                Hq[PQ & 3] = pa.lam * (y - 1);
-                Hq[(PQ + 1) & 3] = pa.lam * y;
-                Hq[(PQ + 2) & 3] = pa.lam * (y + 1);
-                Hr[PQ & 3] = f16x2_int(Hq[PQ & 3]);
-                Hr[(PQ + 1) & 3] = f16x2_int(Hq[(PQ + 1) & 3]);
-                Hr[(PQ + 2) & 3] = f16x2_int(Hq[(PQ + 2) & 3]);
+              if constexpr (HT) {
+                // and what was fetched for the steps after this one restarts too
+                const int32_t q1 = pa.lam * (y + 1);
+                Hr[PQ & 3] = h_tab(q1 - 2 * pa.lam);
+                Hr[(PQ + 1) & 3] = h_tab(q1 - pa.lam);
+                Hr[(PQ + 2) & 3] = h_tab(q1);
+#pragma unroll
+                for (int j = (PQ & 3) + 1; j < 4; ++j) Hn[j] = h_tab(q1 + (j - (PQ & 3)) * pa.lam);
+                hg = q1 + (3 - (PQ & 3)) * pa.lam;
+                if constexpr ((PQ & 3) >= 2) h_tab4(std::bool_constant<L1>{}, hg + pa.lam, Hp);  // already fetched (step 2)
               } else {
                 Hr[PQ & 3] = h_bits(pa.lam * (y - 1));
                 Hr[(PQ + 1) & 3] = h_bits(pa.lam * y);
@@ -1009,9 +1085,8 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
 #endif
       };
       if constexpr (VS) {
-        if constexpr (TSA_H_SALU) {
-          Hq[(PQ + 2) & 3] = Hq[(PQ + 1) & 3] + pa.lam;
-          Hr[(PQ + 2) & 3] = f16x2_int(Hq[(PQ + 2) & 3]);
+        if constexpr (HT) {
+          Hr[(PQ + 2) & 3] = Hn[PQ & 3];
         } else {
           Hr[(PQ + 2) & 3] = U(H(Hr[(PQ + 1) & 3]) + H(pa.v_lam));
         }
@@ -1058,6 +1133,15 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
         } else if constexpr (TSA_ABL_ZREC) {
           zmove_abl<M>(svIyz, rz);
           zmove_abl<M>(svM[PH], rw);
+        } else if constexpr (RP && ROLE == 3) {  // every position holds the face itself, H(t + 1)
+#pragma unroll
+          for (int i = 0; i < M; ++i) {
+            svIyz[i] = rz[i];
+            svM[PH][i] = rw[i];
+          }
+        } else if constexpr (RP) {  // read at position k - 1: lane 0's halves alone
+          zfix<M>(svIyz, rz, sel, Hr[(PQ + 1) & 3]);
+          zfix<M>(svM[PH], rw, sel, Hr[(PQ + 1) & 3]);
         } else {
           zshift<M>(svIyz, rz, sel, Hr[(PQ + 1) & 3]);
           zshift<M>(svM[PH], rw, sel, Hr[(PQ + 1) & 3]);
@@ -1115,7 +1199,12 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VMW) : "memory");
       }
       // skew 2: a wave reads records two steps old, so one barrier per pair of steps
-      if constexpr (HSK == 1 || PH == 1) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      // (HT: the group's last barrier names the fetched H values, so the wait
+      // the compiler owes them stands here, where lgkmcnt(0) is waited for anyway)
+      if constexpr (HT && PQ == 3)
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier"
+                     : "+s"(Hp[0]), "+s"(Hp[1]), "+s"(Hp[2]), "+s"(Hp[3])::"memory");
+      else if constexpr (HSK == 1 || PH == 1) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     };
 
     // the last step is peeled off (it records the final cell), so the loop
@@ -1139,6 +1228,15 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
         auto group_bases = [&]() {  // the A addresses of the group's first step
           abase = a_lane + 4u * (uint32_t)xpos0;
           if constexpr (A_B64) abase_s = a_lane_s + 4u * (uint32_t)xpos0;
+          if constexpr (HT) {  // the values fetched in the last group become this one's
+            hg += 4 * pa.lam;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) Hn[j] = Hp[j];
+          }
+          if constexpr (RP && (decltype(role)::value & 3) == 0) {  // wave 0: slots (t & 4) .. + 3 (t % 4 == 0)
+            r0_own = rd_base + (t & 4) * SLOT_BYTES;
+            r0_prev = rd_prev + (t & 4) * SLOT_BYTES;
+          }
         };
         if constexpr (FIRSTLAP && (decltype(role)::value & 3) == 0) {
           // wave 0's first lap: whole groups in the first-lap role (no fetch, no
@@ -1189,10 +1287,21 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
     constexpr int W0 = (M == 2 && TSA_IS_STATIC) ? 4 : 0, W1 = (M == 2 && TSA_IS_STATIC) ? 8 : 0;
     static_assert(NW % 2 == 0, "the last wave is odd");
     if constexpr (PRE) vs_inject(std::integral_constant<int, 0>{});  // step 0's x = 1
-    if (w == 0) TSA_INLINE_IF_WIDE(run(std::integral_constant<int, 0 + W0>{}));
-    else if (w == NW - 1) TSA_INLINE_IF_WIDE(run(std::integral_constant<int, 2 + W1>{}));
-    else if (W0 != 0 && (w & 1)) TSA_INLINE_IF_WIDE(run(std::integral_constant<int, 1 + W1>{}));
-    else TSA_INLINE_IF_WIDE(run(std::integral_constant<int, 1 + W0>{}));
+    // (bit 4, HT: the loop's version for lam = 1, whose four H values of a group
+    // are one four-dword load)
+    auto run_wave = [&](auto l1) {
+      constexpr int LB = decltype(l1)::value ? 16 : 0;
+      if (w == 0) TSA_INLINE_IF_WIDE(run(std::integral_constant<int, 0 + W0 + LB>{}));
+      else if (w == NW - 1) TSA_INLINE_IF_WIDE(run(std::integral_constant<int, 2 + W1 + LB>{}));
+      else if (W0 != 0 && (w & 1)) TSA_INLINE_IF_WIDE(run(std::integral_constant<int, 1 + W1 + LB>{}));
+      else TSA_INLINE_IF_WIDE(run(std::integral_constant<int, 1 + W0 + LB>{}));
+    };
+    if constexpr (HT) {
+      if (pa.lam == 1) run_wave(std::true_type{});
+      else run_wave(std::false_type{});
+    } else {
+      TSA_INLINE_IF_WIDE(run_wave(std::false_type{}));
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -20,6 +20,18 @@ z = 0 face the READER needs -- the writer's own H(t+2) after its lap-wrap
 update, which equals the reader's H(t'+1) two steps later (same u, one row
 down) -- so the reader takes Iyz and M from its record with no z-shift.
 
+`read_prev=True` (V-space, not `shifted`; the kernel's TSA_REC_PREV) replays
+the reader-side address rule: a lane takes {Iyz, best} of the row above from
+the RECORD of position k-1 -- register i-1 of its own lane, or register M-1 of
+lane-1 (lane 63 for lane 0) for register 0 -- and only lane 0's register 0 is
+fixed up after the read ({z = 0 face, lane 63's low half}). No write changes, so
+wave 0 reads the ring rows the same way.
+The emulator has no LDS addresses: this replays the DATA rule only (which
+record's halves each lane and register ends up with), and gives what the
+reader's z-shift gives. The kernel's address arithmetic -- the lane - 1 base,
+the record offsets, wave 0's slot base -- is guarded by the GPU tests alone
+(tests/test_helix_prev_reads.py).
+
 Layout as in the kernel: NW = 8 waves, wave w owns row y = lap*NW + w + 1;
 lane l, register i, half h is position k = 64M h + M l + i (TWO mode, LC <= 64
 and M = 1: k = l, and half h scores its own triple); position k of wave w
@@ -45,7 +57,7 @@ def penalties(go, ge):
 
 
 def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shifted=None, garbage_seed=None,
-            ring_garbage_seed=None):
+            ring_garbage_seed=None, read_prev=False):
     """Scores of one workgroup's unit: one triple, or two (TWO mode: LC <= 64).
     Returns a list of scores (one per triple). `garbage_seed` starts the LDS
     record slots, `ring_garbage_seed` the global ring, with garbage (what an
@@ -54,6 +66,7 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
     two = len(triples) == 2
     shifted = vs if shifted is None else shifted
     assert vs or not shifted
+    assert not read_prev or (vs and not shifted)
     la_, lb_, lc_ = ([len(t[k]) for t in triples] for k in range(3))
     max_la, max_lb, max_lc = max(la_), max(lb_), max(lc_)
     M = 1 if max_lc <= 128 else 2
@@ -155,6 +168,19 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
         out[0, 0, 1] = face if two else v[M - 1, 63, 0]
         return out
 
+    def prev_read(v, face):
+        # TSA_REC_PREV: each (lane, register) reads the record of position k-1 by
+        # its address -- register i-1 of the lane, or register M-1 of lane-1 (mod
+        # 64) -- both halves as they lie there; then lane 0's register 0 takes
+        # {face, lane 63's low half} (TWO: the face in both halves)
+        out = np.empty_like(v)
+        out[1:] = v[:-1]
+        out[0] = np.roll(v[M - 1], 1, axis=0)  # lane l <- lane l-1, lane 0 <- lane 63
+        lane63_low = out[0, 0, 0]
+        out[0, 0, 1] = face if two else lane63_low
+        out[0, 0, 0] = face
+        return out
+
     for t in range(T):
         PH = t & 1
         outs = [None] * NW
@@ -244,6 +270,9 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
                     d["svIyz"] = rec[2].copy()
                     d["svM"][PH] = rec[3].copy()
                     outs[w] = np.stack([out[0], out[1], shift(out[2], h2), shift(out[3], h2)])
+                elif read_prev:
+                    d["svIyz"] = prev_read(rec[2], h1)
+                    d["svM"][PH] = prev_read(rec[3], h1)
                 else:
                     d["svIyz"] = shift(rec[2], h1)
                     d["svM"][PH] = shift(rec[3], h1)

@@ -103,7 +103,11 @@ def main(tag="r1"):
                 # plane: one step = 3L-1 launches of varying size; report per-step total
                 with open(os.path.join(outdir, f"pmc_{kn}_batch.json"), "w") as f:
                     json.dump({"tag": tag, "kernel": big["kernel"], "grid_size": big["grid_size"],
-                               "avg_ns": big["avg_ns"], "hbm_bytes_per_launch": big["hbm_bytes_corrected"],
+                               "avg_ns": big["avg_ns"], "median_ns": big["median_ns"],
+                               "dispatches": big["dispatches"],
+                               "avg_ns_note": "every dispatch of the trace run, warm-ups included (a stamp, "
+                                              "not a timing: see the round's before/after record)",
+                               "hbm_bytes_per_launch": big["hbm_bytes_corrected"],
                                "hbm_bytes_raw": big["hbm_bytes_raw"],
                                "valu_insts_per_launch": big.get("valu_insts"),
                                "kernel_source_sha256": kernel_source_hash(kn),
