@@ -76,6 +76,11 @@ struct PencilArgs {
   int32_t lam;                  // lam as an integer (0: not V-space)
   uint32_t v_lam, v_cP, v_dO;   // lam, GO + MISMATCH + lam, GO - GE
   float d0f, d1f;               // RTL s3 deltas (V-space K = (d0 + [b=c] d1) / code(b))
+  // Integer-pattern V-space cell (cell_messages_vi): a half holds u = bias + 8 V
+  int32_t bias;                 // 0: the float cell
+  uint32_t i_bias;              // bias in both halves
+  uint32_t i_lam, i_cP, i_dO;   // 8 lam, 8 (GO + MISMATCH + lam), 8 (GO - GE): both halves, 32-bit subtrahends
+  int32_t dm8, d0_8, d1_8;      // 8 (match - mismatch), 8 d0, 8 d1 (weights 8 w / code)
 };
 
 
@@ -429,6 +434,75 @@ __device__ __forceinline__ void cell_messages_vs(
   }
 }
 
+// The V-space cell on integer bit patterns (tests/test_cell_int_algebra.py
+// replays it on packed words against the oracle). A half holds the unsigned
+// u = bias + 8 V, kept inside [0x0400, 0x7BFF] by the host (pencil_kernel.hip:
+// use_vi): a positive, normal, finite f16 pattern, for which IEEE order is the
+// unsigned integer order, so every max stays a v_pk_maximum3_f16 and returns the
+// bitwise maximum exactly. What the float cell adds as packed f16 -- SBC, the
+// three - CP, the three - LAM, - DO: constants and per-row registers, never two
+// DP values -- is one 32-bit integer add or subtract of the packed constant
+// (c_hi * 65536 + c_lo, formed in signed arithmetic): both halves come out right
+// while each half's true result lies in [0, 65535], which the window gives.
+// v_add_u32 / v_sub_u32 issue in 2 cycles where every packed op takes 4
+// (tools/valu_peak.hip, profiles/r9_valu_mix.jsonl). Symbol codes are one-hot
+// 1, 2, 4, 8, so a & b is b's code on a match, and the per-row weights DMB =
+// 8 dm / code(b), DMC = 8 dm / code(c), K = 8 (d0 + [b=c] d1) / code(b) are
+// integers (per half, mod 2^16): v_pk_mad_u16 adds a bonus with no carry
+// between the halves. The same 24 operations per register as cell_messages_vs.
+__device__ __forceinline__ uint32_t imax(uint32_t a, uint32_t b) { return U(hmax(H(a), H(b))); }
+__device__ __forceinline__ uint32_t imax3(uint32_t a, uint32_t b, uint32_t c) {
+  return U(vmax3(H(a), H(b), H(c)));
+}
+// Per half: (w8 / code) mod 2^16 for a one-hot code 1, 2, 4 or 8 (w8 a multiple
+// of 8), 0 for code 0 (padding).
+__device__ __forceinline__ uint32_t w8_over_code(int32_t w8, uint32_t codes) {
+  uint32_t r = 0;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int32_t c = (int32_t)((codes >> (16 * h)) & 0xFFFFu);
+    if (c != 0) r |= ((uint32_t)(w8 / c) & 0xFFFFu) << (16 * h);
+  }
+  return r;
+}
+// Two 16-bit two's-complement halves -> the word a 32-bit add needs to add both
+// (hi * 65536 + lo in signed arithmetic): a negative low half borrows from the high.
+__device__ __forceinline__ uint32_t pk_signed(uint32_t v) { return v - ((v & 0x8000u) << 1); }
+template <int M, bool SOP>
+__device__ __forceinline__ void cell_messages_vi(
+    const uint32_t (&a)[M], const uint32_t (&b)[M], const uint32_t (&c)[M],
+    const uint32_t (&SBC)[M], const uint32_t (&K)[M], const uint32_t (&DMC)[M], const uint32_t (&DMB)[M],
+    const PencilArgs &pa,
+    const uint32_t (&inIx)[M], const uint32_t (&inIy)[M], const uint32_t (&inIz)[M],
+    const uint32_t (&inIxy)[M], const uint32_t (&inIyz)[M], const uint32_t (&inIxz)[M],
+    const uint32_t (&inM)[M], uint32_t (&nIx)[M], uint32_t (&oIy)[M], uint32_t (&oIz)[M],
+    uint32_t (&oIxy)[M], uint32_t (&oIyz)[M], uint32_t (&oIxz)[M], uint32_t (&oBest)[M]) {
+  const uint32_t LAM = pa.i_lam, CP = pa.i_cP, DO = pa.i_dO;
+#pragma unroll
+  for (int i = 0; i < M; ++i) {
+    const uint32_t eab = a[i] & b[i], eac = a[i] & c[i];
+    const uint32_t sXY = pk_mad(eab, DMB[i], inIxy[i]);
+    const uint32_t sXZ = pk_mad(eac, DMC[i], inIxz[i]);
+    const uint32_t sYZ = inIyz[i] + SBC[i];  // SBC, SOP's K: pk_signed words
+    uint32_t sM;
+    if constexpr (SOP) sM = pk_mad(eab, DMB[i], pk_mad(eac, DMC[i], inM[i])) + K[i];
+    else sM = pk_mad(eab, K[i], inM[i]);
+    const uint32_t sX = inIx[i], sY = inIy[i], sZ = inIz[i];
+    const uint32_t Gx = imax3(sY, sZ, sYZ), Gy = imax3(sX, sZ, sXZ), Gz = imax3(sX, sY, sXY);
+    const uint32_t best = imax3(Gx, Gy, imax(sXY, sM));
+    const uint32_t b1 = best - DO;
+    const uint32_t pXY = imax(Gz, b1), pYZ = imax(Gx, b1), pXZ = imax(Gy, b1);
+    const uint32_t qXY = pXY - CP, qYZ = pYZ - CP, qXZ = pXZ - CP;
+    oBest[i] = best;
+    oIxy[i] = pXY;
+    oIyz[i] = pYZ;
+    oIxz[i] = pXZ;
+    nIx[i] = imax3(sX - LAM, qXY, qXZ);
+    oIy[i] = imax3(sY - LAM, qXY, qYZ);
+    oIz[i] = imax3(sZ - LAM, qYZ, qXZ);
+  }
+}
+
 // Shift a packed per-position value one position up the helix (k <- k-1).
 // With k = 64M*h + M*lane + i, register i >= 1 takes register i-1 of the same
 // lane (a rename, no instruction); register 0 takes register M-1 of lane-1
@@ -524,7 +598,8 @@ __device__ __forceinline__ void pos_split(int32_t k, int32_t &l, int32_t &i, int
   } while (0)
 
 // Host: packed constants of a parameter set (pencil_kernel.hip).
-PencilArgs make_args(const KParams &kp, bool f16, bool vs);
+// vi_bias: the integer-pattern V-space cell's bias (0: the float cell)
+PencilArgs make_args(const KParams &kp, bool f16, bool vs, int32_t vi_bias = 0);
 
 // Instantiated helix shapes: M = 1, 2, 4, 8 pairs per lane (LC up to 128 M),
 // 8 rows per workgroup; each in f16 / int16 arithmetic and RTL / SOP s3.

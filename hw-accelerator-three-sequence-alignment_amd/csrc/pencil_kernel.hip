@@ -308,6 +308,7 @@ static bool pencil_shape_ok(int32_t max_la, int32_t max_lb, int32_t max_lc) {
 
 static bool use_f16(const KParams &kp, const Range &r);
 static bool use_vs(const KParams &kp, const Range &r, int32_t max_la, int32_t max_lb, int32_t max_lc);
+static int32_t use_vi(const KParams &kp, const Range &r, int32_t max_la, int32_t max_lb, int32_t max_lc);
 
 // Estimated latency (us) of the helix kernel for a batch: dispatch waves x
 // steps per triple x step time. Measured: a fully loaded chip (two 8-wave
@@ -407,7 +408,10 @@ bool pencil_shape_supported(int32_t max_la, int32_t max_lb, int32_t max_lc) {
 // V-space f16 cell (cell_messages_vs): every value shifted by lam*(x+y+z), the
 // zero faces injected as lam*q (x = 1: H(t), H(t-1); z = 0: H(t+1), H(t+2);
 // y = 0: the ring's face records), the score shifted back at the end.
-template <int M, int NW, bool F16, bool SOP, bool TWO, bool VS>
+// VI: the V-space cell on integer bit patterns (cell_messages_vi): every half
+// holds bias + 8 V, the symbol codes are 1 << s, the per-row terms integer
+// weights. Records, ring, z-shifts and injections move bits and do not change.
+template <int M, int NW, bool F16, bool SOP, bool TWO, bool VS, bool VI = false>
 __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restrict__ seqs,
                                                          const int64_t *__restrict__ offs,
                                                          int32_t n, int32_t P, int32_t R,
@@ -434,10 +438,19 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   static_assert(!TWO || M == 1, "two triples per wave: 64 positions, M = 1");
   static_assert(!VS || (F16 && M <= 2), "V-space: the f16 helix with the four-step loop");
-  // f16 bits of an integer (|v| <= 2048: exact), in both halves
-  auto h_bits = [](int32_t v) -> uint32_t {
+  static_assert(!VI || (VS && M == 2 && !TWO && helix_skew(M) == 2 && !TSA_H_TAB && !TSA_SHIFTED_REC && !TSA_PREINJ),
+                "integer patterns: the V-space M = 2 helix at skew 2");
+  constexpr uint32_t SYMC = VI ? 1u : SYM0;  // symbol codes SYMC << s
+  // f16 bits of an integer (|v| <= 2048: exact), in both halves; VI: bias + 8 v
+  auto h_bits = [&](int32_t v) -> uint32_t {
+    if constexpr (VI) return (uint32_t)(pa.bias + 8 * v) * 0x00010001u;
     const _Float16 h = (_Float16)(float)v;
     return (uint32_t)__builtin_bit_cast(uint16_t, h) * 0x00010001u;
+  };
+  // per-half weight w / code of a one-hot code (the match bonus' multiplier)
+  auto w_over_code = [&](float wf, int32_t w8, uint32_t codes) -> uint32_t {
+    if constexpr (VI) return w8_over_code(w8, codes);
+    else return dm_over_code(wf, codes);
   };
   // TWO: the halves are two triples at the same position, so lane 0 takes its
   // whole word from the z = 0 face (no half crosses from lane 63)
@@ -509,8 +522,8 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
     // B; face records in the ring
     auto a_entry = [&](int j) -> uint32_t {  // periodic in j: the pad repeats P
       const int x0 = ((j - ZT) % P + P) % P, x1 = TWO ? x0 : ((j - ZT - 64 * M) % P + P) % P;
-      const uint32_t c0 = x0 < la ? SYM0 << tsa_sym(seqs, o0 + x0, pa.packed) : 0u;
-      const uint32_t c1 = x1 < la1 ? SYM0 << tsa_sym(seqs, (TWO ? q0 : o0) + x1, pa.packed) : 0u;
+      const uint32_t c0 = x0 < la ? SYMC << tsa_sym(seqs, o0 + x0, pa.packed) : 0u;
+      const uint32_t c1 = x1 < la1 ? SYMC << tsa_sym(seqs, (TWO ? q0 : o0) + x1, pa.packed) : 0u;
       return c0 | (c1 << 16);
     };
     for (int j = threadIdx.x; j < P + ZT + A_PAD; j += 64 * NW) {
@@ -519,10 +532,10 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
     }
     for (int i = threadIdx.x; i < lbm; i += 64 * NW) {
       if constexpr (TWO)
-        sB[i] = (i < lb ? SYM0 << tsa_sym(seqs, o1 + i, pa.packed) : 0u) |
-                ((i < lb1 ? SYM0 << tsa_sym(seqs, q1 + i, pa.packed) : 0u) << 16);
+        sB[i] = (i < lb ? SYMC << tsa_sym(seqs, o1 + i, pa.packed) : 0u) |
+                ((i < lb1 ? SYMC << tsa_sym(seqs, q1 + i, pa.packed) : 0u) << 16);
       else
-        sB[i] = (SYM0 << tsa_sym(seqs, o1 + i, pa.packed)) * 0x00010001u;
+        sB[i] = (SYMC << tsa_sym(seqs, o1 + i, pa.packed)) * 0x00010001u;
     }
     // ring rows of wave 0's lap 0 -> ring row (t - lag) mod R at step t
     const int32_t lag = P - HSK * (NW - 1);
@@ -566,16 +579,16 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
 #pragma unroll
     for (int i = 0; i < M; ++i) {
       const int k0 = M * lane + i, k1 = TWO ? k0 : 64 * M + M * lane + i;
-      const uint32_t c0 = k0 < lc ? SYM0 << tsa_sym(seqs, o2 + k0, pa.packed) : 0u;
-      const uint32_t c1 = k1 < lc1 ? SYM0 << tsa_sym(seqs, (TWO ? q2 : o2) + k1, pa.packed) : 0u;
+      const uint32_t c0 = k0 < lc ? SYMC << tsa_sym(seqs, o2 + k0, pa.packed) : 0u;
+      const uint32_t c1 = k1 < lc1 ? SYMC << tsa_sym(seqs, (TWO ? q2 : o2) + k1, pa.packed) : 0u;
       c[i] = c0 | (c1 << 16);
-      DMC[i] = dm_over_code(pa.dmf, c[i]);
+      DMC[i] = w_over_code(pa.dmf, pa.dm8, c[i]);
       b[i] = SBC[i] = K[i] = DMB[i] = 0;  // set when a position reaches x = 1 of its lap
       oIx[i] = pa.f_single;
       shIz[i] = pa.f_single;
       shIxz[0][i] = shIxz[1][i] = pa.f_pair;
       svIxy[i] = svIyz[i] = pa.f_pair;
-      svM[0][i] = svM[1][i] = 0;
+      svM[0][i] = svM[1][i] = VI ? pa.i_bias : 0u;  // (VI: f_single, f_pair are the bias too)
     }
     // position-0 bookkeeping (wave-uniform): u0 = t - w
     int32_t xpos0 = (P - ((HSK * w) % P)) % P;  // (t - HSK w) mod P at t = 0
@@ -606,10 +619,10 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
         // min): DMB = dm / code(b) and, RTL, K = (d0 + [b=c] d1) / code(b)
         uint32_t kb0 = k0v, kbd = kdv;
         if constexpr (VS) {
-          DMBn = dm_over_code(pa.dmf, binj);
+          DMBn = w_over_code(pa.dmf, pa.dm8, binj);
           if constexpr (!SOP) {
-            kb0 = dm_over_code(pa.d0f, binj);
-            const uint32_t kb1 = dm_over_code(pa.d0f + pa.d1f, binj);
+            kb0 = w_over_code(pa.d0f, pa.d0_8, binj);
+            const uint32_t kb1 = w_over_code(pa.d0f + pa.d1f, pa.d0_8 + pa.d1_8, binj);
             kbd = (((kb1 & 0xFFFFu) - (kb0 & 0xFFFFu)) & 0xFFFFu) | ((((kb1 >> 16) - (kb0 >> 16)) & 0xFFFFu) << 16);
           }
         }
@@ -618,6 +631,10 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
           const uint32_t e01 = pk_eq1(binj, c[i], one1);
           SBCn[i] = pk_mad(e01, sbcv, 0u);
           Kn[i] = pk_mad(e01, kbd, kb0);
+          if constexpr (VI) {  // what a 32-bit add adds: the words of the signed halves
+            SBCn[i] = pk_signed(SBCn[i]);
+            if constexpr (SOP) Kn[i] = pk_signed(Kn[i]);
+          }
         }
       }
     };
@@ -677,7 +694,8 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
       } else {
         Hr[0] = h_bits(hq_at(0));
         Hr[1] = h_bits(hq_at(1));
-        Hr[3] = U(H(Hr[0]) - H(pa.v_lam));
+        if constexpr (VI) Hr[3] = Hr[0] - pa.i_lam;
+        else Hr[3] = U(H(Hr[0]) - H(pa.v_lam));
       }
       if (w == 0) {  // position 0's z = 0 faces at steps 0 and 1 (as if shifted in at steps -1, -2)
 #pragma unroll
@@ -884,7 +902,9 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
         for (int i = 0; i < M; ++i) {
           if (ISC >= 0 ? i == ISC : i == is) {
             if constexpr (VS) {  // faces (0,y,z), (0,y-1,z), (0,y,z-1): lam(y+z-1); (0,y-1,z-1): one lam less
-              if constexpr (HT) {
+              // (VI: H is a wave-uniform integer a scalar add advances, so it
+              // lives in SGPRs with no load, and the bfi reads it from there)
+              if constexpr (HT || VI) {
                 inIx[i] = vbfi_s(m1, Hr[PQ & 3], inIx[i]);
                 inIxy[i] = vbfi_s(m1, Hr[PQ & 3], inIxy[i]);
                 inIxz[i] = vbfi_s(m1, Hr[PQ & 3], inIxz[i]);
@@ -928,7 +948,10 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
       // of a SIMD finish each step first and idle at the barrier (+3-4 %).
       if constexpr (TSA_SETPRIO) __builtin_amdgcn_s_setprio(0);
       if constexpr (TSA_SCHED_FENCE) __builtin_amdgcn_sched_barrier(0);  // keep the arithmetic between the two
-      if constexpr (VS)
+      if constexpr (VI)
+        cell_messages_vi<M, SOP>(a, b, c, SBC, K, DMC, DMB, pv, inIx, inIy, inIz, inIxy, inIyz, inIxz, inM, nIx,
+                                 oIy, oIz, oIxy, oIyz, oIxz, oBest);
+      else if constexpr (VS)
         cell_messages_vs<M, SOP>(a, b, c, SBC, K, DMC, DMB, pv, inIx, inIy, inIz, inIxy, inIyz, inIxz, inM, nIx,
                                  oIy, oIz, oIxy, oIyz, oIxz, oBest);
       else if constexpr (F16)
@@ -1087,6 +1110,8 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
       if constexpr (VS) {
         if constexpr (HT) {
           Hr[(PQ + 2) & 3] = Hn[PQ & 3];
+        } else if constexpr (VI) {
+          Hr[(PQ + 2) & 3] = Hr[(PQ + 1) & 3] + pa.i_lam;
         } else {
           Hr[(PQ + 2) & 3] = U(H(Hr[(PQ + 1) & 3]) + H(pa.v_lam));
         }
@@ -1306,6 +1331,7 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
     __syncthreads();
     if (threadIdx.x == 0) {
       auto decode = [&](uint16_t hb) -> int32_t {
+        if constexpr (VI) return ((int32_t)hb - pa.bias) / 8;  // u = bias + 8 V
         return F16 ? (int32_t)(float)__builtin_bit_cast(_Float16, hb) : (int32_t)(int16_t)hb;
       };
       // VS: the final cell's value sits lam (la + lb + lc) above its score
@@ -1332,7 +1358,7 @@ static uint32_t pkh(double v) {  // both halves = f16(v); v exactly representabl
   return (uint32_t)bits * 0x00010001u;
 }
 
-PencilArgs make_args(const KParams &kp, bool f16, bool vs) {
+PencilArgs make_args(const KParams &kp, bool f16, bool vs, int32_t vi_bias) {
   const int32_t GE = kp.pen[SIXY][SIX], GO = kp.pen[SIXY][SM];  // Ixy row: Ix = GE, M = GO
   int32_t fs = -kp.pen[SIX][0], fp = -kp.pen[SIXY][0];
   for (int s = 0; s < 7; ++s) {
@@ -1387,6 +1413,20 @@ PencilArgs make_args(const KParams &kp, bool f16, bool vs) {
       a.h_k0 = k0v;
       a.h_kd = (((k1v & 0xFFFF) - (k0v & 0xFFFF)) & 0xFFFF) * 0x00010001u;
     }
+    if (vi_bias != 0) {  // cell_messages_vi: u = bias + 8 V, everything scaled by 8
+      a.bias = vi_bias;
+      a.i_bias = (uint32_t)vi_bias * 0x00010001u;
+      a.i_lam = (uint32_t)(8 * GE) * 0x00010001u;
+      a.i_cP = (uint32_t)(8 * (GO + mm + GE)) * 0x00010001u;
+      a.i_dO = (uint32_t)(8 * (GO - GE)) * 0x00010001u;
+      a.dm8 = 8 * dm;
+      a.d0_8 = 8 * d0;
+      a.d1_8 = 8 * d1;
+      a.f_single = a.f_pair = a.i_bias;  // initial register contents: an in-window pattern
+      a.h_sbc = pk16(8 * dm);             // SBC = e01 * 8 dm per half (pk_signed in the kernel)
+      a.h_k0 = pk16(8 * (3 * mm + 3 * GE));  // SOP's K = 8 (3 mismatch + 3 lam + dm [b=c])
+      a.h_kd = pk16(8 * dm);
+    }
   }
   return a;
 }
@@ -1435,6 +1475,48 @@ static bool use_vs(const KParams &kp, const Range &r, int32_t max_la, int32_t ma
   return r.lo - slack >= -2048 && hi <= 2048 && (int64_t)GO + GE + kp.mismatch <= 2048;
 }
 
+// The integer-pattern V-space cell (cell_messages_vi), consulted only where
+// use_vs holds: the bias, or 0 where the float cell stays. Restricted to the
+// case TSA_REC_PREV is restricted to (M = 2, not TWO, skew 2). Every half of a
+// started position must stay inside [0x0400, 0x7BFF] (a carry out of a low half
+// would reach a live high half), padding and run-on cells included. Those are
+// cells too: a padding symbol's code is 0, which matches nothing, so the
+// positions at x > LA (up to the lap period P), z > LC (up to 128 M) and in the
+// rows y > LB a wave still starts before the final step (fewer than 2 NW of
+// them) compute the DP of the triple extended to (P, LB + 2 NW, 128 M) by
+// symbols that never match, with that problem's own faces lam q. value_bound
+// assumes nothing about the symbols, so the extended problem's bound holds for
+// them: r was proven for (max_la, max_lb, max_lc) and is linear in the shortest
+// length (lower end) and in the coordinate sum (upper end), and is rescaled
+// here, each end rounded outward. For LA = P and LC = 128 M (the 256^3 batch)
+// only the 2 NW rows are added. The face values H = lam q (q <= the extended
+// sum) lie under the upper end. Widened by pencil_slack for the - 8 CP, - 8 LAM
+// and bonus intermediates, scaled by 8, the interval must fit the window.
+// pencil_arith = f16vf keeps the float cell; f16vi is refused where this is 0.
+#ifndef TSA_VI_DEFAULT  // the integer cell wherever it is admitted (0: only under f16vi)
+#define TSA_VI_DEFAULT 1
+#endif
+constexpr int32_t VI_LO = 0x0400, VI_HI = 0x7BFF;
+// the build's switches leave the form the integer cell is written for (else it is not instantiated)
+constexpr bool VI_BUILT = TSA_REC_PREV && !TSA_H_TAB && !TSA_SHIFTED_REC && !TSA_PREINJ && TSA_SKEW == 2 &&
+                          PENCIL_NW == 8;
+static int32_t use_vi(const KParams &kp, const Range &r, int32_t max_la, int32_t max_lb, int32_t max_lc) {
+  if (arith_override("f16vf") || !use_vs(kp, r, max_la, max_lb, max_lc)) return 0;
+  if (!TSA_VI_DEFAULT && !arith_override("f16vi")) return 0;
+  const PencilGeom g = pencil_geom(max_la, max_lc);
+  if (!VI_BUILT || g.M != 2 || g.two) return 0;
+  const int32_t GE = kp.pen[SIXY][SIX], GO = kp.pen[SIXY][SM];
+  const int64_t e_la = g.P, e_lb = (int64_t)max_lb + 2 * helix_nw(g.M), e_lc = 128 * g.M;
+  const int64_t mn = std::min<int64_t>(max_la, std::min(max_lb, max_lc)), e_mn = std::min(e_la, std::min(e_lb, e_lc));
+  const int64_t q = (int64_t)max_la + max_lb + max_lc, e_q = e_la + e_lb + e_lc;
+  const int64_t lo = -((-std::min<int64_t>(r.lo, 0) * e_mn + mn - 1) / mn);  // r.lo <= 0, linear in mn
+  const int64_t hi = ((std::max<int64_t>(r.hi, 0) + 1) * e_q + q - 1) / q;   // r.hi = floor(gain q)
+  const int64_t slack = pencil_slack(kp.match, kp.mismatch, GO, GE);
+  const int64_t v_lo = lo - slack, v_hi = hi + (int64_t)GE * e_q + slack;
+  if (8 * (v_hi - v_lo) > VI_HI - VI_LO) return 0;
+  return (int32_t)(VI_LO - 8 * v_lo);
+}
+
 // The lap kernel's V-space cell (lap_kernel VS) under the same conditions as
 // the helix's, for any tile width: lam = GE = -MISMATCH and the shifted
 // values exact f16 integers.
@@ -1466,6 +1548,9 @@ static int launch_m(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n,
   const bool two = M == 1 && g.two;
   auto kfn = vs ? (two ? pencil_kernel<M, NW, F16, SOP, M == 1, VSOK> : pencil_kernel<M, NW, F16, SOP, false, VSOK>)
                 : (two ? pencil_kernel<M, NW, F16, SOP, M == 1, false> : pencil_kernel<M, NW, F16, SOP, false, false>);
+  if constexpr (VSOK && M == 2 && VI_BUILT) {  // the integer-pattern cell (use_vi set the bias)
+    if (vs && pa.bias != 0) kfn = pencil_kernel<M, NW, F16, SOP, false, VSOK, true>;
+  }
   if (lds > LDS_MAX) return TSA_EINVAL;
   const int32_t units = two ? (n + 1) / 2 : n;
   const int grid = units < 65535 ? units : 65535;
@@ -1493,8 +1578,9 @@ void pencil_describe(int32_t n, int32_t max_la, int32_t max_lb, int32_t max_lc, 
   }
   const PencilGeom g = pencil_geom(max_la, max_lc);
   if (use_vs(kp, bound, max_la, max_lb, max_lc)) arith = "f16v";  // the helix's V-space cell
+  const bool vi = !checked && use_vi(kp, bound, max_la, max_lb, max_lc) != 0;  // on integer patterns
   snprintf(buf, len, "pencil helix %s %s M=%d NW=%d P=%d%s est=%.0fus", arith, s3, g.M, helix_nw(g.M), g.P,
-           g.two ? " two" : "", helix_est(n, max_la, max_lb, max_lc));
+           g.two ? " two" : vi ? " int" : "", helix_est(n, max_la, max_lb, max_lc));
 }
 
 int pencil_launch_batch(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n,
@@ -1508,13 +1594,15 @@ int pencil_launch_batch(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t
   const bool f16 = chk ? false : use_f16(kp, bound);  // the checked kernel runs int16
   const bool sop = kp.s3_mode == TSA_S3_SOP;
   const LapGeom lg = lap_choice(n, max_la, max_lb, max_lc, lap, f16, sop, chk != nullptr);
+  const int32_t vi_bias = chk ? 0 : use_vi(kp, bound, max_la, max_lb, max_lc);
+  if (arith_override("f16vi") && (lg.ok || vi_bias == 0)) return TSA_EINVAL;  // no integer cell for this launch
   if (lg.ok) {
     if (ws_bytes < lap_workspace_bytes(lg)) return TSA_ENOMEM;
     const bool lvs = f16 && lap_vs_ok(kp, bound, max_la, max_lb, max_lc);
     return lap_launch(lg, f16, sop, d_seqs, d_offsets, n, d_scores, d_ws, make_args(kp, f16, lvs), stream,
                       d_err, chk);
   }
-  const PencilArgs pa = make_args(kp, f16, !chk && use_vs(kp, bound, max_la, max_lb, max_lc));
+  const PencilArgs pa = make_args(kp, f16, !chk && use_vs(kp, bound, max_la, max_lb, max_lc), vi_bias);
   if (chk) return TSA_ERANGE;  // no lap schedule for this batch
   const PencilGeom g = pencil_geom(max_la, max_lc);
   const int32_t grid = n < 65535 ? n : 65535;

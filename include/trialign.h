@@ -513,6 +513,9 @@ const char *tsa_version(void);
  * scores stay exact under every override (only speed and the plan change).
  *   pencil_mode     helix | lap | plane | literal | litlap
  *   pencil_arith    i16 | f16       (factored arithmetic: int16, f16 w/o V-space)
+ *                   f16vf | f16vi   (the V-space helix: f16vf keeps the float
+ *                   cell; f16vi asks for the cell on integer bit patterns and
+ *                   is TSA_EINVAL for a launch that cannot run it)
  *   pencil_two      0 | 1           (two triples per helix wave for LC <= 64)
  *   lap_m, lap_nw   lap tile pairs per lane (1,2,4) / compute waves (4,8)
  *   lap_vs          0 | 1           (the lap kernel's V-space cell)

@@ -32,6 +32,19 @@ reader's z-shift gives. The kernel's address arithmetic -- the lane - 1 base,
 the record offsets, wave 0's slot base -- is guarded by the GPU tests alone
 (tests/test_helix_prev_reads.py).
 
+`int_bits=True` (with `vs` and `read_prev`, M = 2; the kernel's integer-pattern
+cell, cell_messages_vi) carries what the registers hold: every half is the
+16-bit pattern u = bias + 8 V, a register the 32-bit word of its two halves.
+The cell's constant adds and subtracts are done on the 32-bit word, the match
+bonuses per half mod 2^16 (v_pk_mad_u16), every max on the halves as unsigned
+16-bit integers; symbol codes are 1 << s and the per-row weights 8 w / code.
+LDS and ring garbage are random 16-bit patterns. Two events are counted into
+the `events` dict: "window", a half of a started position (t >= S w + k)
+leaving [0x0400, 0x7BFF] after an operation of the cell, and "carry", an add or
+subtract whose low half carried or borrowed while the high half beside it held
+a started position. `bias` defaults to the host predicate's (vi_bias below, the
+rule of use_vi in csrc/pencil_kernel.hip); the other modes are unchanged.
+
 Layout as in the kernel: NW = 8 waves, wave w owns row y = lap*NW + w + 1;
 lane l, register i, half h is position k = 64M h + M l + i (TWO mode, LC <= 64
 and M = 1: k = l, and half h scores its own triple); position k of wave w
@@ -56,15 +69,60 @@ def penalties(go, ge):
                      [go, ge, go, ge, go, go, ge]], dtype=np.int64)
 
 
+VI_LO, VI_HI = 0x0400, 0x7BFF
+
+
+def value_bound(la, lb, lc, match, mismatch, go, ge, sop):
+    """csrc/trialign_api.hip value_bound: [lo, hi] of every state and candidate."""
+    Pen = penalties(go, ge)
+    m, mm = match, mismatch
+    s3v = [3 * m, m + 2 * mm, 3 * mm] if sop else [3 * m, 2 * (m + mm), 3 * mm]
+    s3max, s3min, s2max, s2min = max(s3v), min(s3v), max(m, mm), min(m, mm)
+    scmax = [s3max, 0, 0, 0, s2max, s2max, s2max]
+    scmin = [s3min, 0, 0, 0, s2min, s2min, s2min]
+    dq = [3, 1, 1, 1, 2, 2, 2]
+    gain = max(0.0, max((scmax[T] - int(Pen[T][s])) / dq[T] for T in range(7) for s in range(7)))
+    hi = int(np.floor(gain * (la + lb + lc) + 1e-9))
+    bestlo = min(la, lb, lc) * min(0, s3min)
+    drop = max(0, max(int(Pen[T].max()) - scmin[T] for T in range(7)))
+    cdrop = max(0, max(int(Pen[T][s]) - scmin[T] for T in range(7) for s in range(7)))
+    return min(0, bestlo - drop) - cdrop, max(hi, 0)
+
+
+def vi_bias(max_la, max_lb, max_lc, match=1, mismatch=-1, go=2, ge=1, sop=False):
+    """The bias use_vi (csrc/pencil_kernel.hip) gives the integer-pattern cell,
+    or 0 where it keeps the float cell: the proven range rescaled to the triple
+    extended to (P, LB + 2 NW, 128 M) by symbols that never match, widened by
+    pencil_slack and lam times the extended coordinate sum, times 8, inside
+    [0x0400, 0x7BFF]. (Of use_vs' own conditions only lam = GE = -MISMATCH >= 1,
+    GO >= GE, 128 < LC <= 256 and the f16 range are repeated here.)"""
+    if not (128 < max_lc <= 256) or ge < 1 or ge != -mismatch or go < ge or abs(match - mismatch) > 7:
+        return 0
+    lo, hi = value_bound(max_la, max_lb, max_lc, match, mismatch, go, ge, sop)
+    slack = 8 * max(abs(match), abs(mismatch)) + 4 * max(abs(go), abs(ge))
+    q = max_la + max_lb + max_lc
+    if lo - slack < -2048 or hi + ge * q + slack > 2048:
+        return 0
+    P = -(-max(max_la, 256) // 4) * 4
+    e = (P, max_lb + 2 * NW, 256)
+    mn, e_mn, e_q = min(max_la, max_lb, max_lc), min(e), sum(e)
+    lo_e = -((-min(lo, 0) * e_mn + mn - 1) // mn)
+    hi_e = ((max(hi, 0) + 1) * e_q + q - 1) // q
+    v_lo, v_hi = lo_e - slack, hi_e + ge * e_q + slack
+    if 8 * (v_hi - v_lo) > VI_HI - VI_LO:
+        return 0
+    return VI_LO - 8 * v_lo
+
+
 def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shifted=None, garbage_seed=None,
-            ring_garbage_seed=None, read_prev=False):
+            ring_garbage_seed=None, read_prev=False, int_bits=False, bias=None, events=None):
     """Scores of one workgroup's unit: one triple, or two (TWO mode: LC <= 64).
     Returns a list of scores (one per triple). `garbage_seed` starts the LDS
     record slots, `ring_garbage_seed` the global ring, with garbage (what an
     earlier launch left in the workspace): a ring row read before this unit
     wrote it then spoils the score."""
     two = len(triples) == 2
-    shifted = vs if shifted is None else shifted
+    shifted = (vs and not read_prev) if shifted is None else shifted
     assert vs or not shifted
     assert not read_prev or (vs and not shifted)
     la_, lb_, lc_ = ([len(t[k]) for t in triples] for k in range(3))
@@ -79,6 +137,15 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
     R = P + RING_EXTRA
     lam = ge if vs else 0
     assert not vs or ge == -mismatch
+    assert not int_bits or (vs and read_prev and M == 2 and not two)
+    if int_bits and bias is None:
+        bias = vi_bias(max_la, max_lb, max_lc, match, mismatch, go, ge, sop)
+        assert bias, "use_vi's rule refuses this shape and parameter set"
+    if events is None:
+        events = {}
+    events.setdefault("window", 0)
+    events.setdefault("carry", 0)
+    enc = (lambda v: (bias + 8 * v) & 0xFFFF) if int_bits else (lambda v: v)  # a V value as the registers hold it
     Pen = penalties(go, ge)
     f_single, f_pair = -int(Pen[1].min()), -int(Pen[4].min())
     dm = match - mismatch
@@ -116,7 +183,7 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
 
     def face_rec(tr):  # the y = 0 row as wave 0 meets it at step tr
         if vs:
-            return np.array([lam * (tr + 1), lam * (tr + 2), lam * (tr + 2), lam * (tr + 2)])
+            return np.array([enc(lam * (tr + 1)), enc(lam * (tr + 2)), enc(lam * (tr + 2)), enc(lam * (tr + 2))])
         return np.array([f_single, f_pair, f_pair, 0])
 
     # V-space: wave 0 builds the face records of its steps [0, t_sw) from its own
@@ -126,12 +193,13 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
     t_sw = (max(lag - PD, 0) & ~3) if vs else 0
     ring = np.zeros((R, 4) + shape, np.int64)     # [R, 4, M, 64, 2]
     if ring_garbage_seed is not None:
-        ring = np.random.default_rng(ring_garbage_seed).integers(-3000, 3000, ring.shape)
+        ring = np.random.default_rng(ring_garbage_seed).integers(*((0, 1 << 16) if int_bits else (-3000, 3000)),
+                                                                 ring.shape)
     for tr in (range(t_sw + FILL_FROM, lag) if vs else range(lag, lag + R)):
         ring[(tr - lag) % R] = face_rec(tr % R)[:, None, None, None] * np.ones((1,) + shape, np.int64)
     xr = np.zeros((NW, 4, 4) + shape, np.int64)    # [wave][slot][field]
     if garbage_seed is not None:  # LDS starts with whatever the last kernel left
-        xr = np.random.default_rng(garbage_seed).integers(-3000, 3000, xr.shape)
+        xr = np.random.default_rng(garbage_seed).integers(*((0, 1 << 16) if int_bits else (-3000, 3000)), xr.shape)
     if shifted:  # wave 0 seeds lane 0's shifted {Iyz, best} of steps -2, -1 (slots 2, 3): the z = 0
         # face wave 1's position 0 takes at its first steps (H_0(0), H_0(1); no record precedes them)
         for slot, v in ((2, lam * 1), (3, lam * 2)):
@@ -141,10 +209,11 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
     for w in range(NW):
         xpos0 = (P - (S * w) % P) % P
         lap0 = 0 if w == 0 else -1
-        d = dict(oIx=np.full(shape, f_single), shIz=np.full(shape, f_single),
-                 svIxy=np.full(shape, f_pair), svIyz=np.full(shape, f_pair),
-                 shIxz=[np.full(shape, f_pair), np.full(shape, f_pair)],
-                 svM=[np.zeros(shape, np.int64), np.zeros(shape, np.int64)],
+        i_s, i_p, i_m = (bias, bias, bias) if int_bits else (f_single, f_pair, 0)  # (int: in-window patterns)
+        d = dict(oIx=np.full(shape, i_s), shIz=np.full(shape, i_s),
+                 svIxy=np.full(shape, i_p), svIyz=np.full(shape, i_p),
+                 shIxz=[np.full(shape, i_p), np.full(shape, i_p)],
+                 svM=[np.full(shape, i_m, np.int64), np.full(shape, i_m, np.int64)],
                  b=np.full(shape, -1), xpos0=xpos0, lap0=lap0)
         if vs:  # H(s) = lam (y + xpos0) at step s, H(-1) := H(0) - lam
             def h_at(s, w=w):
@@ -153,9 +222,9 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
                 return lam * (lp * NW + w + 1 + (u - lp * P))
             d["H"] = {0: h_at(0), 1: h_at(1), -1: h_at(0) - lam}
             if w == 0:  # position 0's z = 0 faces at steps 0 and 1 ("shifted in" at steps -1, -2)
-                d["shIz"][:] = d["svIyz"][:] = d["H"][0]
-                d["shIxz"][1][:] = d["H"][1]
-                d["svM"][1][:] = d["H"][0]
+                d["shIz"][:] = d["svIyz"][:] = enc(d["H"][0])
+                d["shIxz"][1][:] = enc(d["H"][1])
+                d["svM"][1][:] = enc(d["H"][0])
         st.append(d)
 
     def shift(v, face):
@@ -187,7 +256,8 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
         for w in range(NW):
             d = st[w]
             if w == 0 and t < t_sw:  # {H(t), H(t + 1) x 3} in every position
-                rec = np.array([d["H"][t], d["H"][t + 1], d["H"][t + 1], d["H"][t + 1]])[:, None, None, None] * \
+                rec = np.array([enc(d["H"][t]), enc(d["H"][t + 1]), enc(d["H"][t + 1]),
+                                enc(d["H"][t + 1])])[:, None, None, None] * \
                     np.ones((1,) + shape, np.int64)
             else:
                 rec = ring[(t - lag) % R] if w == 0 else xr[w - 1, (t - S) & 3]
@@ -204,14 +274,56 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
                 b = np.where(inj, bn, b)
                 d["b"] = b
                 if vs:
-                    inIx[inj] = inIxy[inj] = inIxz[inj] = d["H"][t]
-                    inM[inj] = d["H"][t - 1]
+                    inIx[inj] = inIxy[inj] = inIxz[inj] = enc(d["H"][t])
+                    inM[inj] = enc(d["H"][t - 1])
                 else:
                     inIx[inj], inIxy[inj], inIxz[inj], inM[inj] = f_single, f_pair, f_pair, 0
             eab = (acode >= 0) & (acode == b)
             eac = (acode >= 0) & (acode == ccode)
             ebc = (b >= 0) & (b == ccode)
-            if vs:
+            if int_bits:
+                started = (t - S * w - kpos) >= 0
+                mx = np.maximum
+
+                def seen(v):  # a started half outside the window
+                    events["window"] += int((started & ((v < VI_LO) | (v > VI_HI))).sum())
+                    return v
+
+                def wadd(v, cst):  # one 32-bit add of the packed constant (signed halves cst)
+                    cst = np.broadcast_to(np.asarray(cst, np.int64), shape)
+                    low = v[..., 0] + cst[..., 0]
+                    events["carry"] += int((((low < 0) | (low > 0xFFFF)) & started[..., 1]).sum())
+                    word = (v[..., 0] + (v[..., 1] << 16) + cst[..., 0] + cst[..., 1] * 65536) & 0xFFFFFFFF
+                    return seen(np.stack([word & 0xFFFF, word >> 16], -1))
+
+                def mad(e_, w_, v):  # v_pk_mad_u16: per half, mod 2^16
+                    return seen((e_ * (w_ & 0xFFFF) + v) & 0xFFFF)
+
+                def over(w8, codes):  # 8 w / code per half, 0 for code 0
+                    return np.where(codes > 0, w8 // np.maximum(codes, 1), 0)
+
+                ca, cb, cc = (np.where(v >= 0, 1 << np.maximum(v, 0), 0) for v in (acode, b, ccode))
+                e_ab, e_ac = ca & cb, ca & cc
+                DMB, DMC = over(8 * dm, cb), over(8 * dm, cc)
+                d0, d1 = 2 * (match + mismatch) - 3 * mismatch, 3 * match - 2 * (match + mismatch)
+                sXY, sXZ = mad(e_ab, DMB, inIxy), mad(e_ac, DMC, inIxz)
+                sYZ = wadd(inIyz, 8 * dm * ebc)
+                if sop:
+                    sM = wadd(mad(e_ab, DMB, mad(e_ac, DMC, inM)), 8 * (3 * mismatch + 3 * lam + dm * ebc))
+                else:
+                    sM = mad(e_ab, over(8 * (d0 + d1 * ebc), cb), inM)
+                sX, sY, sZ = inIx, inIy, inIz
+                Gx, Gy, Gz = mx(mx(sY, sZ), sYZ), mx(mx(sX, sZ), sXZ), mx(mx(sX, sY), sXY)
+                best = mx(mx(Gx, Gy), mx(sXY, sM))
+                b1 = wadd(best, -8 * (go - ge))
+                pXY, pYZ, pXZ = mx(Gz, b1), mx(Gx, b1), mx(Gy, b1)
+                c8 = -8 * (go + mismatch + lam)
+                qXY, qYZ, qXZ = wadd(pXY, c8), wadd(pYZ, c8), wadd(pXZ, c8)
+                nIx = mx(wadd(sX, -8 * lam), mx(qXY, qXZ))
+                oIy = mx(wadd(sY, -8 * lam), mx(qXY, qYZ))
+                oIz = mx(wadd(sZ, -8 * lam), mx(qYZ, qXZ))
+                oIxy, oIyz, oIxz = pXY, pYZ, pXZ
+            elif vs:
                 sXY, sXZ, sYZ = inIxy + dm * eab, inIxz + dm * eac, inIyz + dm * ebc
                 if sop:
                     sM = inM + dm * (eab.astype(np.int64) + ebc + eac) + 3 * mismatch + 3 * lam
@@ -263,7 +375,7 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
                     y = d["lap0"] * NW + w + 1
                     d["H"][t], d["H"][t + 1], d["H"][t + 2] = lam * (y - 1), lam * y, lam * (y + 1)
             if vs:
-                h1, h2 = d["H"][t + 1], d["H"][t + 2]
+                h1, h2 = enc(d["H"][t + 1]), enc(d["H"][t + 2])
                 d["shIxz"][PH] = shift(oIxz, h2)
                 d["shIz"] = shift(oIz, h1)
                 if shifted:  # the writer shifted the record; its face is h2 (see above)
@@ -285,4 +397,6 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
             xr[w, t & 3] = outs[w]
         ring[t % R] = outs[NW - 1]
     shifts = [lam * (len(a) + len(b) + len(c)) for (a, b, c) in (triples if two else triples[:1])]
+    if int_bits:
+        fin = [(f - bias) // 8 for f in fin]
     return [f - s for f, s in zip(fin, shifts)]

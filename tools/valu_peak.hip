@@ -6,6 +6,16 @@
 // 4 for one wave alone): v_fma_f32, v_max3_f32, v_max_i32, v_add_u32,
 // v_pk_max_i16, v_pk_add_u16, v_pk_fma_f32, v_max3_i16, v_perm_b32.
 // 1, 2, 4 and 8 waves per SIMD, independent chains (8 accumulators per wave).
+//
+// Round 9 adds the integer kinds an integer-bit-pattern V-space cell would
+// issue (v_sub_u32, v_and_b32, v_add3_u32, v_pk_mad_u16, v_pk_min_u16, v_bfi_b32
+// with an SGPR source) and mixed dependent chains on the same accumulators:
+// max3 then v_add_u32, max3 then v_pk_add_f16, and the cell's proportions
+// (22 max3 : 16 add : 6 mad : 4 and) in an integer and a float form. It also
+// checks that v_pk_maximum3_f16 on patterns in [0x0400, 0x7BFF] is the unsigned
+// 16-bit maximum bit for bit, and that v_pk_mad_u16 carries nothing between
+// halves. `valu_peak --gate` runs only the check and the mixes at 4 waves per
+// SIMD, three times each, and prints the gate line.
 //   hipcc -O3 --offload-arch=gfx950 tools/valu_peak.hip -o tools/valu_peak && tools/valu_peak
 // Prints one JSON line per (op, waves/SIMD): G wave-instr/s over the chip and
 // instructions per cycle per SIMD at the measured in-kernel clock.
@@ -13,6 +23,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #define CHK(x)                                                                  \
   do {                                                                          \
@@ -25,10 +36,39 @@
 
 constexpr int ITERS = 4096;  // loop trips; 8 rounds of 8 accumulators each per trip
 
+enum {
+  OP_SUB_U32 = 13, OP_AND_B32, OP_ADD3_U32, OP_PK_MAD_U16, OP_PK_MIN_U16, OP_BFI_SGPR,
+  MIX_MAX3_ADDU32, MIX_MAX3_PKADD, MIX_CELL_INT, MIX_CELL_F16, OP_PERM
+};
+
+// wave-instructions one loop trip issues
+constexpr int per_trip(int op) {
+  return op == MIX_MAX3_ADDU32 || op == MIX_MAX3_PKADD ? 128
+         : op == MIX_CELL_INT || op == MIX_CELL_F16    ? 384
+                                                       : 64;
+}
+
+// One instruction kind applied to all 8 accumulators.
+#define ALL8(S)                                                                            \
+  asm volatile(S : "+v"(v0) : "v"(k), "v"(k2)); asm volatile(S : "+v"(v1) : "v"(k), "v"(k2)); \
+  asm volatile(S : "+v"(v2) : "v"(k), "v"(k2)); asm volatile(S : "+v"(v3) : "v"(k), "v"(k2)); \
+  asm volatile(S : "+v"(v4) : "v"(k), "v"(k2)); asm volatile(S : "+v"(v5) : "v"(k), "v"(k2)); \
+  asm volatile(S : "+v"(v6) : "v"(k), "v"(k2)); asm volatile(S : "+v"(v7) : "v"(k), "v"(k2));
+#define MX ALL8("v_pk_maximum3_f16 %0, %0, %1, %0")
+#define AI ALL8("v_add_u32 %0, %0, %1")
+#define AF ALL8("v_pk_add_f16 %0, %0, %1")
+#define FI ALL8("v_pk_mad_u16 %0, %2, %1, %0")
+#define FF ALL8("v_pk_fma_f16 %0, %2, %1, %0")
+#define ND ALL8("v_and_b32 %0, %0, %1")
+// 11 max3 : 8 add : 3 mad : 2 and, in the order a cell interleaves them; twice
+// per trip is the cell's 22 : 16 : 6 : 4.
+#define CELL24(A, F) MX A MX A MX F MX A MX A MX ND MX A MX A MX F MX A MX A F ND
+
 template <int OP>
 __global__ void valu_loop(unsigned *out, unsigned seed, unsigned long long *clk) {
   unsigned v0 = seed ^ threadIdx.x, v1 = v0 + 1, v2 = v0 + 2, v3 = v0 + 3, v4 = v0 + 4,
-           v5 = v0 + 5, v6 = v0 + 6, v7 = v0 + 7, k = seed * 3u;
+           v5 = v0 + 5, v6 = v0 + 6, v7 = v0 + 7, k = seed * 3u, k2 = seed * 5u + threadIdx.x;
+  const unsigned ks = seed * 7u;  // wave-uniform: lives in an SGPR
   // packed-f32 accumulators (64-bit VGPR pairs) for v_pk_fma_f32
   double d0 = v0, d1 = v1, d2 = v2, d3 = v3, d4 = v4, d5 = v5, d6 = v6, d7 = v7, kd = 0.5;
   const unsigned long long t0 = __builtin_amdgcn_s_memtime();
@@ -60,11 +100,35 @@ __global__ void valu_loop(unsigned *out, unsigned seed, unsigned long long *clk)
     asm volatile("v_pk_fma_f32 %0, %0, %1, %0" : "+v"(d##I) : "v"(kd));                      \
   else if constexpr (OP == 11)                                                                \
     asm volatile("v_max3_i16 %0, %0, %1, %0" : "+v"(v##I) : "v"(k));                         \
+  else if constexpr (OP == OP_SUB_U32)                                                        \
+    asm volatile("v_sub_u32 %0, %0, %1" : "+v"(v##I) : "v"(k));                              \
+  else if constexpr (OP == OP_AND_B32)                                                        \
+    asm volatile("v_and_b32 %0, %0, %1" : "+v"(v##I) : "v"(k));                              \
+  else if constexpr (OP == OP_ADD3_U32)                                                       \
+    asm volatile("v_add3_u32 %0, %0, %1, %1" : "+v"(v##I) : "v"(k));                         \
+  else if constexpr (OP == OP_PK_MAD_U16)                                                     \
+    asm volatile("v_pk_mad_u16 %0, %0, %1, %0" : "+v"(v##I) : "v"(k));                       \
+  else if constexpr (OP == OP_PK_MIN_U16)                                                     \
+    asm volatile("v_pk_min_u16 %0, %0, %1" : "+v"(v##I) : "v"(k));                           \
+  else if constexpr (OP == OP_BFI_SGPR)                                                       \
+    asm volatile("v_bfi_b32 %0, %1, %2, %0" : "+v"(v##I) : "v"(k), "s"(ks));                 \
   else                                                                                        \
     asm volatile("v_perm_b32 %0, %0, %1, %1" : "+v"(v##I) : "v"(k));
+    if constexpr (OP == MIX_MAX3_ADDU32) {
 #pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      BODY(0) BODY(1) BODY(2) BODY(3) BODY(4) BODY(5) BODY(6) BODY(7)
+      for (int r = 0; r < 8; ++r) { MX AI }
+    } else if constexpr (OP == MIX_MAX3_PKADD) {
+#pragma unroll
+      for (int r = 0; r < 8; ++r) { MX AF }
+    } else if constexpr (OP == MIX_CELL_INT) {
+      CELL24(AI, FI) CELL24(AI, FI)
+    } else if constexpr (OP == MIX_CELL_F16) {
+      CELL24(AF, FF) CELL24(AF, FF)
+    } else {
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        BODY(0) BODY(1) BODY(2) BODY(3) BODY(4) BODY(5) BODY(6) BODY(7)
+      }
     }
 #undef BODY
   }
@@ -78,8 +142,47 @@ __global__ void valu_loop(unsigned *out, unsigned seed, unsigned long long *clk)
   }
 }
 
+// Every (a, b) pair of patterns in [0x0400, 0x7BFF] in the low half, with a
+// hashed third operand and a permuted triple in the high half: the packed f16
+// max3 must be the unsigned 16-bit max of each half, and the packed u16 mad
+// must be each half's own product-sum mod 2^16.
+constexpr unsigned WLO = 0x0400u, WHI = 0x7BFFu, WN = WHI - WLO + 1u;
+__global__ void check_patterns(unsigned long long *bad) {
+  const unsigned a = WLO + blockIdx.x;
+  unsigned nmax = 0, nmad = 0;
+  for (unsigned b = WLO + threadIdx.x; b <= WHI; b += blockDim.x) {
+    const unsigned c = WLO + (a * 2654435761u + b * 40503u) % WN;
+    const unsigned pa = (b << 16) | a, pb = (c << 16) | b, pc = (a << 16) | c;
+    unsigned r;
+    asm volatile("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(pa), "v"(pb), "v"(pc));
+    const unsigned m = max(a, max(b, c));
+    nmax += r != ((m << 16) | m);
+    const unsigned e = (b & 15u) | ((c & 15u) << 16), w = 0xFFF8u | (24u << 16);
+    asm volatile("v_pk_mad_u16 %0, %1, %2, %3" : "=v"(r) : "v"(e), "v"(w), "v"(pa));
+    const unsigned lo = ((e & 0xFFFFu) * (w & 0xFFFFu) + a) & 0xFFFFu;
+    const unsigned hi = ((e >> 16) * (w >> 16) + b) & 0xFFFFu;
+    nmad += r != ((hi << 16) | lo);
+  }
+  if (nmax) atomicAdd(&bad[0], (unsigned long long)nmax);
+  if (nmad) atomicAdd(&bad[1], (unsigned long long)nmad);
+}
+
+static bool check() {
+  unsigned long long *bad, h[2];
+  CHK(hipMalloc(&bad, 16));
+  CHK(hipMemset(bad, 0, 16));
+  hipLaunchKernelGGL(check_patterns, dim3(WN), dim3(256), 0, 0, bad);
+  CHK(hipDeviceSynchronize());
+  CHK(hipMemcpy(h, bad, 16, hipMemcpyDeviceToHost));
+  CHK(hipFree(bad));
+  printf("{\"check\": \"patterns 0x0400..0x7BFF\", \"pairs\": %llu, \"max3_f16_ne_umax\": %llu, "
+         "\"pk_mad_u16_ne_halves\": %llu}\n",
+         (unsigned long long)WN * WN, h[0], h[1]);
+  return h[0] == 0 && h[1] == 0;
+}
+
 template <int OP>
-static void run(const char *name, int waves_per_simd, int cus) {
+static double run(const char *name, int waves_per_simd, int cus, int pass = -1) {
   const int threads = 256 * (waves_per_simd < 4 ? waves_per_simd : 4);  // <= 1024 per WG
   const int wgs_per_cu = waves_per_simd <= 4 ? 1 : waves_per_simd / 4;
   const int grid = cus * wgs_per_cu;
@@ -104,20 +207,50 @@ static void run(const char *name, int waves_per_simd, int cus) {
   CHK(hipMemcpy(hclk, clk, 16, hipMemcpyDeviceToHost));
   const double ghz = hclk[1] ? (double)hclk[0] / (double)hclk[1] * 0.1 : 0.0;  // memrealtime 100 MHz
   const double waves = (double)grid * threads / 64.0;
-  const double instr = waves * ITERS * 64.0 * reps;  // wave-instructions
+  const double instr = waves * ITERS * (double)per_trip(OP) * reps;  // wave-instructions
   const double rate = instr / (ms * 1e-3);
   const double per_simd_cycle = ghz > 0 ? rate / (cus * 4.0) / (ghz * 1e9) : 0.0;
   printf("{\"op\": \"%s\", \"waves_per_simd\": %d, \"G_wave_instr_per_s\": %.1f, \"clock_ghz\": %.3f, "
-         "\"instr_per_cycle_per_simd\": %.3f}\n",
+         "\"instr_per_cycle_per_simd\": %.3f",
          name, waves_per_simd, rate / 1e9, ghz, per_simd_cycle);
+  if (pass >= 0) printf(", \"pass\": %d", pass);
+  printf("}\n");
   CHK(hipFree(out));
   CHK(hipFree(clk));
+  return rate / 1e9;
 }
 
-int main() {
+// The gate of the integer cell: at 4 waves per SIMD the integer mix must beat
+// the float mix by more than the probe's own spread, three passes of each.
+static void gate(const char *what, const double (&fl)[3], const double (&in)[3]) {
+  double fmin = fl[0], fmax = fl[0], imin = in[0], imax = in[0];
+  for (int i = 1; i < 3; ++i) {
+    fmin = fl[i] < fmin ? fl[i] : fmin, fmax = fl[i] > fmax ? fl[i] : fmax;
+    imin = in[i] < imin ? in[i] : imin, imax = in[i] > imax ? in[i] : imax;
+  }
+  const double spread = (fmax - fmin) > (imax - imin) ? fmax - fmin : imax - imin;
+  printf("{\"gate\": \"%s\", \"waves_per_simd\": 4, \"float_min\": %.1f, \"float_max\": %.1f, "
+         "\"int_min\": %.1f, \"int_max\": %.1f, \"spread\": %.1f, \"int_over_float\": %.4f, "
+         "\"passed\": %s}\n",
+         what, fmin, fmax, imin, imax, spread, (in[0] + in[1] + in[2]) / (fl[0] + fl[1] + fl[2]),
+         imin - fmax > spread ? "true" : "false");
+}
+
+int main(int argc, char **argv) {
   hipDeviceProp_t prop;
   CHK(hipGetDeviceProperties(&prop, 0));
   const int cus = prop.multiProcessorCount;
+  const bool ok = check();
+  double pf[3], pi[3], cf[3], ci[3];
+  for (int p = 0; p < 3; ++p) {
+    pf[p] = run<MIX_MAX3_PKADD>("max3_f16+pk_add_f16", 4, cus, p);
+    pi[p] = run<MIX_MAX3_ADDU32>("max3_f16+add_u32", 4, cus, p);
+    cf[p] = run<MIX_CELL_F16>("cell 22 max3:16 pk_add_f16:6 pk_fma_f16:4 and", 4, cus, p);
+    ci[p] = run<MIX_CELL_INT>("cell 22 max3:16 add_u32:6 pk_mad_u16:4 and", 4, cus, p);
+  }
+  gate("pair 1:1", pf, pi);
+  gate("cell mix", cf, ci);
+  if (argc > 1 && !strcmp(argv[1], "--gate")) return ok ? 0 : 1;
   for (int w : {1, 2, 4, 8}) {
     run<0>("v_pk_maximum3_f16", w, cus);
     run<1>("v_pk_add_f16", w, cus);
@@ -131,7 +264,17 @@ int main() {
     run<9>("v_pk_add_u16", w, cus);
     run<10>("v_pk_fma_f32", w, cus);
     run<11>("v_max3_i16", w, cus);
-    run<12>("v_perm_b32", w, cus);
+    run<OP_PERM>("v_perm_b32", w, cus);
+    run<OP_SUB_U32>("v_sub_u32", w, cus);
+    run<OP_AND_B32>("v_and_b32", w, cus);
+    run<OP_ADD3_U32>("v_add3_u32", w, cus);
+    run<OP_PK_MAD_U16>("v_pk_mad_u16", w, cus);
+    run<OP_PK_MIN_U16>("v_pk_min_u16", w, cus);
+    run<OP_BFI_SGPR>("v_bfi_b32 sgpr", w, cus);
+    run<MIX_MAX3_ADDU32>("max3_f16+add_u32", w, cus);
+    run<MIX_MAX3_PKADD>("max3_f16+pk_add_f16", w, cus);
+    run<MIX_CELL_INT>("cell 22 max3:16 add_u32:6 pk_mad_u16:4 and", w, cus);
+    run<MIX_CELL_F16>("cell 22 max3:16 pk_add_f16:6 pk_fma_f16:4 and", w, cus);
   }
-  return 0;
+  return ok ? 0 : 1;
 }
