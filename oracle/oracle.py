@@ -59,6 +59,10 @@ def lib() -> ctypes.CDLL:
         L.tsao_best_range.argtypes = three + [pp, ctypes.c_int32, ctypes.c_int32, i32p, i32p,
                                               i32p, i32p, i64p, i64p]
         L.tsao_best_range.restype = ctypes.c_int
+        L.tsao_candidate_range.argtypes = three + [pp, i32p, i32p, i32p, i32p, i32p, i32p]
+        L.tsao_candidate_range.restype = ctypes.c_int
+        L.tsao_candidate_range_all.argtypes = [ctypes.c_int32] * 3 + [pp, i32p, i32p, i64p, i64p]
+        L.tsao_candidate_range_all.restype = ctypes.c_int
         L.tsao_penalty_table.argtypes = [pp, i32p]
         L.tsao_penalty_table.restype = None
         L.tsao_s2.argtypes = [ctypes.c_int, ctypes.c_int, pp]
@@ -169,6 +173,55 @@ def best_range(a, b, c, params: OracleParams | None = None, hi_thr: int = 2**31 
         raise ValueError(f"oracle rc={rc}")
     return BestRange(int(lo.value), int(hi.value), tuple(int(v) for v in amin),
                      tuple(int(v) for v in amax), int(na.value), int(nb.value))
+
+
+class CandidateRange(NamedTuple):
+    """tsao_candidate_range: the unwrapped literal recurrence's 49 candidates of
+    every real cell, and every state (the faces' zeros included)."""
+    lo: int
+    hi: int
+    state_lo: int  # the states alone (what state_range returns)
+    state_hi: int
+    at_lo: tuple   # (x, y, z, target, source) of the first candidate attaining lo;
+    at_hi: tuple   # (0, 0, 0, -1, -1) when the extreme is the faces' zero
+
+
+def candidate_range(a, b, c, params: OracleParams | None = None) -> CandidateRange:
+    """Range of the values the RTL's candidate wires carry before MAX7
+    (src/PE_1cyc.v:127-133,164-218), score_bits ignored: what value_bound of
+    DESIGN.md 1.2 has to cover."""
+    p = params or default_params()
+    A, B, C = _u8(a), _u8(b), _u8(c)
+    lo, hi, slo, shi = (ctypes.c_int32(0) for _ in range(4))
+    amin, amax = (ctypes.c_int32 * 5)(), (ctypes.c_int32 * 5)()
+    rc = lib().tsao_candidate_range(_p(A, ctypes.c_uint8), len(A), _p(B, ctypes.c_uint8), len(B),
+                                    _p(C, ctypes.c_uint8), len(C), ctypes.byref(p),
+                                    ctypes.byref(lo), ctypes.byref(hi), ctypes.byref(slo),
+                                    ctypes.byref(shi), amin, amax)
+    if rc:
+        raise ValueError(f"oracle rc={rc}")
+    return CandidateRange(int(lo.value), int(hi.value), int(slo.value), int(shi.value),
+                          tuple(int(v) for v in amin), tuple(int(v) for v in amax))
+
+
+def triple_number(i: int, la: int, lb: int, lc: int) -> tuple:
+    """Triple number i of candidate_range_all's enumeration."""
+    s = np.array([(i >> (2 * k)) & 3 for k in range(la + lb + lc)], dtype=np.uint8)
+    return s[:la], s[la:la + lb], s[la + lb:]
+
+
+def candidate_range_all(la: int, lb: int, lc: int, params: OracleParams | None = None):
+    """tsao_candidate_range_all: (lo, hi, triple_lo, triple_hi) over every
+    triple of these lengths over the symbols 0..3 (la + lb + lc <= 12); the
+    triples are numbers for triple_number()."""
+    p = params or default_params()
+    lo, hi = ctypes.c_int32(0), ctypes.c_int32(0)
+    ilo, ihi = ctypes.c_int64(0), ctypes.c_int64(0)
+    rc = lib().tsao_candidate_range_all(la, lb, lc, ctypes.byref(p), ctypes.byref(lo), ctypes.byref(hi),
+                                        ctypes.byref(ilo), ctypes.byref(ihi))
+    if rc:
+        raise ValueError(f"oracle rc={rc}")
+    return int(lo.value), int(hi.value), int(ilo.value), int(ihi.value)
 
 
 def penalty_table(params: OracleParams | None = None) -> np.ndarray:

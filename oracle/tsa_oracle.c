@@ -455,6 +455,111 @@ int tsao_state_range(const uint8_t *a, int32_t la, const uint8_t *b, int32_t lb,
   return msg_sweep(a, la, b, lb, c, lc, p, NULL, lo, hi);
 }
 
+/* ---- candidate-range probe ---------------------------------------------------
+ * What the RTL wraps is not a state but each of the 49 wordsize-wide candidate
+ * wires of a cell, S[s] - P[T][s] + score_T (src/PE_1cyc.v:127-133,164-218),
+ * before MAX7 picks among them (src/PE_1cyc.v:1-32). This is the literal
+ * x-plane sweep with score_bits forced to 0, folding every candidate of every
+ * real cell (x, y, z >= 1) and every state -- the zero states of the faces
+ * included (src/TriAlign_1cyc.v:155-182), so lo <= 0 <= hi -- into a range.
+ * Cells are visited in (x, y, z) order, targets and sources in state order,
+ * and the comparisons are strict: at_lo / at_hi name the first candidate
+ * attaining each extreme, {0, 0, 0, -1, -1} when it is the faces' zero. */
+int tsao_candidate_range(const uint8_t *a, int32_t la, const uint8_t *b, int32_t lb,
+                         const uint8_t *c, int32_t lc, const tsa_params *p, int32_t *lo,
+                         int32_t *hi, int32_t *state_lo, int32_t *state_hi, int32_t *at_lo,
+                         int32_t *at_hi) {
+  int rc = check_args(a, la, b, lb, c, lc, p);
+  if (rc) return rc;
+  if (!lo || !hi) return TSA_EINVAL;
+  tsa_params pw = *p;
+  pw.score_bits = 0;
+  int32_t P[7][7];
+  tsao_penalty_table(&pw, P);
+  const size_t W = (size_t)lc + 1, H = (size_t)lb + 1;
+  const size_t plane = W * H * 7;
+  int32_t *prev = (int32_t *)calloc(plane, sizeof(int32_t)); /* x-1; x=0 face = 0 */
+  int32_t *cur = (int32_t *)calloc(plane, sizeof(int32_t));  /* y=0/z=0 faces stay 0 */
+  if (!prev || !cur) { free(prev); free(cur); return TSA_ENOMEM; }
+  int32_t s3_tab[4][4][4], s2_tab[4][4]; /* src/PE_1cyc.v:159-162 */
+  for (int u = 0; u < 4; ++u)
+    for (int v = 0; v < 4; ++v) {
+      s2_tab[u][v] = tsao_s2(u, v, &pw);
+      for (int w = 0; w < 4; ++w) s3_tab[u][v][w] = tsao_s3(u, v, w, &pw);
+    }
+  int64_t clo = 0, chi = 0;
+  int32_t slo = 0, shi = 0, amin[5] = {0, 0, 0, -1, -1}, amax[5] = {0, 0, 0, -1, -1};
+  for (int32_t x = 1; x <= la; ++x) {
+    const int ax = a[x - 1] & 3;
+    for (int32_t y = 1; y <= lb; ++y) {
+      const int by = b[y - 1] & 3;
+      const int32_t *prow = prev + (size_t)y * W * 7, *prow1 = prev + (size_t)(y - 1) * W * 7;
+      int32_t *crow = cur + (size_t)y * W * 7;
+      const int32_t *crow1 = cur + (size_t)(y - 1) * W * 7;
+      for (int32_t z = 1; z <= lc; ++z) {
+        const int cz = c[z - 1] & 3;
+        /* predecessor and added score of each target, as cell_literal wires them */
+        const int32_t *pred[7] = {prow1 + (z - 1) * 7, prow + z * 7,        crow1 + z * 7,
+                                  crow + (z - 1) * 7,  prow1 + z * 7,       crow1 + (z - 1) * 7,
+                                  prow + (z - 1) * 7};
+        const int32_t add[7] = {s3_tab[ax][by][cz], 0, 0, 0, s2_tab[ax][by], s2_tab[by][cz],
+                                s2_tab[ax][cz]};
+        int32_t *out = crow + z * 7;
+        for (int T = 0; T < 7; ++T) {
+          int64_t m = 0;
+          for (int s = 0; s < 7; ++s) {
+            const int64_t v = (int64_t)pred[T][s] - P[T][s] + add[T];
+            if (v < clo) { clo = v; amin[0] = x; amin[1] = y; amin[2] = z; amin[3] = T; amin[4] = s; }
+            if (v > chi) { chi = v; amax[0] = x; amax[1] = y; amax[2] = z; amax[3] = T; amax[4] = s; }
+            if (s == 0 || v > m) m = v;
+          }
+          out[T] = (int32_t)m;
+          if (out[T] < slo) slo = out[T];
+          if (out[T] > shi) shi = out[T];
+        }
+      }
+    }
+    int32_t *t = prev;
+    prev = cur;
+    cur = t;
+  }
+  *lo = (int32_t)clo;
+  *hi = (int32_t)chi;
+  if (state_lo) *state_lo = slo;
+  if (state_hi) *state_hi = shi;
+  if (at_lo) memcpy(at_lo, amin, sizeof(amin));
+  if (at_hi) memcpy(at_hi, amax, sizeof(amax));
+  free(prev);
+  free(cur);
+  return TSA_OK;
+}
+
+/* tsao_candidate_range folded over every one of the 4^(la+lb+lc) triples of
+ * these lengths over the symbols 0..3 (a symbol 4 is the symbol 0: symbols & 3,
+ * src/PE_1cyc.v:63-66). Triple number i has symbol (i >> 2k) & 3 at position k
+ * of a, b, c laid end to end. la + lb + lc <= 12. */
+int tsao_candidate_range_all(int32_t la, int32_t lb, int32_t lc, const tsa_params *p, int32_t *lo,
+                             int32_t *hi, int64_t *triple_lo, int64_t *triple_hi) {
+  if (la < 1 || lb < 1 || lc < 1 || la + lb + lc > 12 || !lo || !hi) return TSA_EINVAL;
+  const int n = la + lb + lc;
+  uint8_t s[12];
+  int32_t rlo = 0, rhi = 0;
+  int64_t ilo = 0, ihi = 0;
+  for (int64_t i = 0; i < ((int64_t)1 << (2 * n)); ++i) {
+    for (int k = 0; k < n; ++k) s[k] = (uint8_t)((i >> (2 * k)) & 3);
+    int32_t l1, h1;
+    int rc = tsao_candidate_range(s, la, s + la, lb, s + la + lb, lc, p, &l1, &h1, NULL, NULL, NULL, NULL);
+    if (rc) return rc;
+    if (i == 0 || l1 < rlo) { rlo = l1; ilo = i; }
+    if (i == 0 || h1 > rhi) { rhi = h1; ihi = i; }
+  }
+  *lo = rlo;
+  *hi = rhi;
+  if (triple_lo) *triple_lo = ilo;
+  if (triple_hi) *triple_hi = ihi;
+  return TSA_OK;
+}
+
 /* ---- batch over POSIX threads -------------------------------------------- */
 typedef struct {
   const uint8_t *seqs;

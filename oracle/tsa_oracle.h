@@ -75,6 +75,27 @@ int tsao_state_range(const uint8_t *a, int32_t la, const uint8_t *b, int32_t lb,
                      const uint8_t *c, int32_t lc, const tsa_params *p,
                      int32_t *lo, int32_t *hi);
 
+/* Min / max over every one of the 49 candidates S[s] - P[T][s] + score_T of
+ * every real cell (x, y, z >= 1) and over every state, the faces' zeros
+ * included, in unbounded arithmetic (score_bits ignored): the values the RTL's
+ * wordsize-wide candidate wires would have to hold (src/PE_1cyc.v:127-133,
+ * 164-218), which is what the a-priori bound of DESIGN.md 1.2 promises to
+ * cover. state_lo / state_hi (nullable): the states alone, as tsao_state_range
+ * gives them. at_lo / at_hi (nullable, 5 ints each): {x, y, z, target, source}
+ * of the first candidate in (x, y, z, target, source) order attaining each
+ * extreme, {0, 0, 0, -1, -1} when it is the faces' zero. */
+int tsao_candidate_range(const uint8_t *a, int32_t la, const uint8_t *b, int32_t lb,
+                         const uint8_t *c, int32_t lc, const tsa_params *p, int32_t *lo,
+                         int32_t *hi, int32_t *state_lo, int32_t *state_hi, int32_t *at_lo,
+                         int32_t *at_hi);
+
+/* The union of tsao_candidate_range over all 4^(la+lb+lc) triples of these
+ * lengths over the symbols 0..3 (la + lb + lc <= 12), and the numbers of the
+ * first triples attaining its ends (nullable): triple i has symbol
+ * (i >> 2k) & 3 at position k of a, b, c laid end to end. */
+int tsao_candidate_range_all(int32_t la, int32_t lb, int32_t lc, const tsa_params *p, int32_t *lo,
+                             int32_t *hi, int64_t *triple_lo, int64_t *triple_hi);
+
 /* Min / max over the real cells (x, y, z >= 1) of the per-cell MAX7 ("best")
  * of the literal recurrence run unwrapped (score_bits forced to 0) -- the
  * quantity the checked kernel's range monitor certifies.

@@ -166,6 +166,89 @@ def test_state_range_small_for_random(orc):
     assert -40 < lo <= 0 <= hi < 40
 
 
+# (match, mismatch, gap_open, gap_extend): the sets whose admission edges
+# tests/test_range_proof.py and tests/test_range_edges_gpu.py visit
+RANGE_SETS = [(1, -1, 2, 1), (2, 0, 2, 1), (3, 1, 2, 1), (40, -1, 2, 1), (10, 8, 2, 1), (0, -2, 3, 2),
+              (-1, -3, 4, 3)]
+
+
+def _py_candidate_range(orc, a, b, c, p):
+    """The recurrence of DESIGN.md 1.1 written out directly from penalty_table,
+    s2 and s3 in Python integers: every candidate S[s] - P[T][s] + score_T of
+    every real cell, every state, and where the extremes are first attained."""
+    P = orc.penalty_table(p).tolist()
+    # offset (dx, dy, dz) of the predecessor each target reads: M, Ix, Iy, Iz, Ixy, Iyz, Ixz
+    step = [(1, 1, 1), (1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (0, 1, 1), (1, 0, 1)]
+    S = {}
+    lo = hi = slo = shi = 0
+    at_lo = at_hi = (0, 0, 0, -1, -1)
+    for x in range(1, len(a) + 1):
+        for y in range(1, len(b) + 1):
+            for z in range(1, len(c) + 1):
+                u, v, w = int(a[x - 1]), int(b[y - 1]), int(c[z - 1])
+                add = [orc.s3(u, v, w, p), 0, 0, 0, orc.s2(u, v, p), orc.s2(v, w, p), orc.s2(u, w, p)]
+                out = []
+                for T, (dx, dy, dz) in enumerate(step):
+                    pred = S.get((x - dx, y - dy, z - dz), [0] * 7)  # a face cell: all states 0
+                    cands = [pred[s] - P[T][s] + add[T] for s in range(7)]
+                    for s, val in enumerate(cands):
+                        if val < lo:
+                            lo, at_lo = val, (x, y, z, T, s)
+                        if val > hi:
+                            hi, at_hi = val, (x, y, z, T, s)
+                    out.append(max(cands))
+                S[(x, y, z)] = out
+                slo, shi = min(slo, *out), max(shi, *out)
+    return (lo, hi, slo, shi, at_lo, at_hi), S[(len(a), len(b), len(c))]
+
+
+@pytest.mark.parametrize("s3_mode", (0, 1))
+@pytest.mark.parametrize("pset", RANGE_SETS, ids=lambda s: "m%d_mm%d_go%d_ge%d" % s)
+def test_candidate_range_against_python_restatement(orc, pset, s3_mode):
+    """tsao_candidate_range against the direct restatement, on cubes up to
+    5 x 4 x 3: the range of the 49 pre-MAX sums of every real cell, the cells,
+    targets and sources attaining it, the state part (equal to state_range),
+    and, from the same Python sweep, the unwrapped score and final states."""
+    m, mm, go, ge = pset
+    p = orc.default_params(match=m, mismatch=mm, gap_open=go, gap_extend=ge, s3_mode=s3_mode, score_bits=0)
+    rng = np.random.default_rng([s3_mode, RANGE_SETS.index(pset)])
+    shapes = [(1, 1, 1), (5, 4, 3), (3, 4, 5), (4, 1, 5), (2, 3, 1)]
+    fams = [lambda n, k: np.zeros(n, np.uint8), lambda n, k: np.full(n, k, np.uint8),
+            lambda n, k: np.full(n, (0, 0, 1)[k], np.uint8), lambda n, k: rng.integers(0, 4, n).astype(np.uint8),
+            lambda n, k: rng.integers(0, 2, n).astype(np.uint8)]
+    for dims in shapes:
+        for fam in fams:
+            a, b, c = (fam(n, k) for k, n in enumerate(dims))
+            want, fin = _py_candidate_range(orc, a, b, c, p)
+            got = orc.candidate_range(a, b, c, p)
+            assert tuple(got) == want, (dims, a, b, c, got, want)
+            assert (got.state_lo, got.state_hi) == orc.state_range(a, b, c, p)
+            assert got.lo <= got.state_lo <= 0 <= got.state_hi <= got.hi
+            assert orc.score(a, b, c, p, final_states=True) == (max(fin), tuple(fin))
+    # score_bits is ignored: a word the values leave does not change the range
+    p8 = orc.default_params(match=m, mismatch=mm, gap_open=go, gap_extend=ge, s3_mode=s3_mode, score_bits=4)
+    assert orc.candidate_range(a, b, c, p8) == got
+
+
+def test_candidate_range_all_is_the_union(orc):
+    """candidate_range_all on (2, 1, 2): the union of candidate_range over the
+    1024 triples, enumerated here in Python, and the first triples attaining it."""
+    import itertools
+    la, lb, lc = 2, 1, 2
+    for pset, s3_mode in ((RANGE_SETS[0], 0), (RANGE_SETS[4], 0), (RANGE_SETS[6], 1)):
+        m, mm, go, ge = pset
+        p = orc.default_params(match=m, mismatch=mm, gap_open=go, gap_extend=ge, s3_mode=s3_mode)
+        each = []
+        for i, s in enumerate(itertools.product(range(4), repeat=5)):
+            s = s[::-1]  # position 0 is the lowest digit of the triple's number
+            r = orc.candidate_range(s[:la], s[la:la + lb], s[la + lb:], p)
+            each.append((r.lo, r.hi))
+            assert [list(t) for t in orc.triple_number(i, la, lb, lc)] == [list(s[:2]), list(s[2:3]), list(s[3:])]
+        los, his = [e[0] for e in each], [e[1] for e in each]
+        want = (min(los), max(his), los.index(min(los)), his.index(max(his)))
+        assert orc.candidate_range_all(la, lb, lc, p) == want
+
+
 def test_generator_matches_python(orc, synth):
     for seed in (synth.SEED_BASE, synth.SEED_BASE + 5, 12345):
         for n in (1, 31, 32, 33, 257):

@@ -45,6 +45,18 @@ subtract whose low half carried or borrowed while the high half beside it held
 a started position. `bias` defaults to the host predicate's (vi_bias below, the
 rule of use_vi in csrc/pencil_kernel.hip); the other modes are unchanged.
 
+A caller that passes `events={"range": {}}` (message form or V-space form, not
+`int_bits`) gets back in that dict the (min, max) of every intermediate the
+halves holding a REAL cell (x <= LA, y <= LB, z <= LC, started) form at a step,
+by group: "in" (the seven inputs of the cell, faces and injections included),
+and for the message form "state" (the seven states), "term" (the 49 differences
+S[s] - P[T][s]) and "msg" (the seven messages); for the V-space form "sum" (the
+inputs plus their match bonuses), "max" (the group maxima, best, best - (GO -
+GE), the pair messages) and "out" (the terms and results of the single-gap
+messages). V-space values are shifted by lam (x + y + z). These are what
+pencil_slack (csrc/pencil_kernel.hip) has to cover around the candidate range
+(tests/test_range_proof.py). Without the key nothing is recorded.
+
 Layout as in the kernel: NW = 8 waves, wave w owns row y = lap*NW + w + 1;
 lane l, register i, half h is position k = 64M h + M l + i (TWO mode, LC <= 64
 and M = 1: k = l, and half h scores its own triple); position k of wave w
@@ -145,6 +157,10 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
         events = {}
     events.setdefault("window", 0)
     events.setdefault("carry", 0)
+    track = events.get("range")  # only a caller that put a dict there gets the value ranges
+    assert track is None or not int_bits
+    lens_h = [np.array([len(trip_[k]) for trip_ in (triples if two else triples * 2)])[None, None, :]
+              for k in range(3)]  # [1, 1, 2]: the lengths of each half's triple
     enc = (lambda v: (bias + 8 * v) & 0xFFFF) if int_bits else (lambda v: v)  # a V value as the registers hold it
     Pen = penalties(go, ge)
     f_single, f_pair = -int(Pen[1].min()), -int(Pen[4].min())
@@ -263,6 +279,18 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
                 rec = ring[(t - lag) % R] if w == 0 else xr[w - 1, (t - S) & 3]
             u = (t - S * w - kpos) % P
             acode = per_half(lambda tr, h: code(tr[0], u))
+            if track is not None:  # the halves that hold a real cell (x <= LA, y <= LB, z <= LC) at this step
+                ua = t - S * w - kpos
+                real = (ua >= 0) & (u < lens_h[0]) & ((ua // P) * NW + w < lens_h[1]) & (kpos < lens_h[2])
+
+                def note(name, *vals):
+                    for v in vals if real.any() else ():  # each [..., M, 64, 2]
+                        v = np.asarray(v)[..., real]
+                        lo_, hi_ = track.get(name, (int(v.min()), int(v.max())))
+                        track[name] = (min(lo_, int(v.min())), max(hi_, int(v.max())))
+            else:
+                def note(name, *vals):
+                    pass
             inIx, inIy, inIz = d["oIx"].copy(), rec[0].copy(), d["shIz"].copy()
             inIxy, inIyz = d["svIxy"].copy(), d["svIyz"].copy()
             inIxz, inM = d["shIxz"][PH].copy(), d["svM"][PH].copy()
@@ -341,6 +369,11 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
                 oIy = mx(sY - lam, mx(pXY, pYZ) - cP)
                 oIz = mx(sZ - lam, mx(pYZ, pXZ) - cP)
                 oIxy, oIyz, oIxz = pXY, pYZ, pXZ
+                note("in", inM, inIx, inIy, inIz, inIxy, inIyz, inIxz)
+                note("sum", sXY, sXZ, sYZ, sM)
+                note("max", Gx, Gy, Gz, best, b1, pXY, pYZ, pXZ)
+                note("out", sX - lam, sY - lam, sZ - lam, mx(pXY, pXZ) - cP, mx(pXY, pYZ) - cP,
+                     mx(pYZ, pXZ) - cP, nIx, oIy, oIz)
             else:  # message form, mismatch not folded (integer arithmetic)
                 s2 = lambda e: np.where(e, match, mismatch)
                 if sop:
@@ -351,6 +384,10 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
                                 inIxz + s2(eac)])
                 msg = [(Sst - Pen[T_][:, None, None, None]).max(0) for T_ in range(7)]
                 best, nIx, oIy, oIz, oIxy, oIyz, oIxz = msg
+                note("in", inM, inIx, inIy, inIz, inIxy, inIyz, inIxz)
+                note("state", Sst)
+                note("term", Sst[None] - Pen[:, :, None, None, None])
+                note("msg", *msg)
             for j, (tf, wf, kf) in enumerate(zip(t_fs, w_fs, k_fs)):
                 if t == tf and w == wf:
                     pos = np.argwhere((kpos == kf) & (tri_of == j))[0]
