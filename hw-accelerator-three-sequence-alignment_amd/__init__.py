@@ -66,7 +66,8 @@ EXPORTS = (
     "tsa_score_gpu_multi", "tsa_score_batch_devices", "tsa_set_override", "tsa_get_overrides",
     "tsa_kernel_launch_count", "tsa_align_batch", "tsa_describe_align_plan", "tsa_align_batch_lowmem",
     "tsa_align_batch_grid", "tsa_align_workspace_size", "tsa_align_batch_async", "tsa_align_rows_async",
-    "tsa_align_batch_ends",
+    "tsa_align_batch_ends", "tsa_score_batch_ends", "tsa_score_ends_workspace_size",
+    "tsa_score_batch_ends_async", "tsa_describe_score_ends_plan",
 )
 
 # Plan overrides the library accepts (tsa_set_override; include/trialign.h).
@@ -164,6 +165,13 @@ def _load_lib() -> ctypes.CDLL:
     lib.tsa_align_batch_grid.argtypes = lib.tsa_align_batch.argtypes
     lib.tsa_align_batch_ends.argtypes = [u8p, i64p, ctypes.c_int32, pp, ctypes.c_int32, i32p, u8p, i32p, i32p, i32p,
                                          ctypes.c_int32]
+    lib.tsa_score_batch_ends.argtypes = [u8p, i64p, ctypes.c_int32, pp, ctypes.c_int32, i32p, i32p, ctypes.c_int32]
+    lib.tsa_score_ends_workspace_size.argtypes = [ctypes.c_int32] * 4 + [pp, ctypes.c_int32,
+                                                                        ctypes.POINTER(ctypes.c_size_t)]
+    lib.tsa_score_batch_ends_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int32] * 4 + \
+        [pp, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.tsa_describe_score_ends_plan.argtypes = [ctypes.c_int32] * 4 + [pp, ctypes.c_int32, ctypes.c_char_p,
+                                                                       ctypes.c_size_t]
     szp = ctypes.POINTER(ctypes.c_size_t)
     lib.tsa_align_workspace_size.argtypes = [i64p, ctypes.c_int32, pp, ctypes.c_int32, szp, szp]
     lib.tsa_align_batch_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, i64p, ctypes.c_int32, pp,
@@ -196,7 +204,8 @@ def _load_lib() -> ctypes.CDLL:
                  "tsa_score_gpu_multi", "tsa_score_batch_devices", "tsa_set_override",
                  "tsa_get_overrides", "tsa_align_batch", "tsa_describe_align_plan",
                  "tsa_align_batch_lowmem", "tsa_align_batch_grid", "tsa_align_workspace_size",
-                 "tsa_align_batch_async", "tsa_align_rows_async", "tsa_align_batch_ends"):
+                 "tsa_align_batch_async", "tsa_align_rows_async", "tsa_align_batch_ends", "tsa_score_batch_ends",
+                 "tsa_score_ends_workspace_size", "tsa_score_batch_ends_async", "tsa_describe_score_ends_plan"):
         getattr(lib, name).restype = ctypes.c_int
     return lib
 
@@ -479,6 +488,76 @@ def align_batch_ends(triples=None, params: Optional[TsaParams] = None, end: str 
     return [(s, tuple(s0), mv[m0:m0 + k].copy(), tuple(e))
             for s, s0, m0, k, e in zip(sc[:n].tolist(), st[:3 * n].reshape(-1, 3).tolist(), at, nm[:n].tolist(),
                                        en[:3 * n].reshape(-1, 3).tolist())]
+
+
+def _end_mode(end, what: str) -> int:
+    mode = END_MODES.get(end, end) if isinstance(end, str) else end
+    if isinstance(mode, (str, bool)) or not isinstance(mode, (int, np.integer)):
+        raise TsaError(TSA_EINVAL, f"{what}(end={end!r})")
+    return int(mode)
+
+
+def score_batch_ends(triples=None, params: Optional[TsaParams] = None, end: str | int = "any", device: int = 0,
+                     seqs: Optional[np.ndarray] = None, offsets: Optional[np.ndarray] = None) -> list:
+    """End-free scores without a path (tsa_score_batch_ends): a list of
+    ``(score, (x1, y1, z1))``, one per triple -- the score and end cell
+    ``align_batch_ends`` returns for the same ``end``, computed by the helix
+    scorer with no memory per cell. The free-end alignment is the corner
+    alignment of ``a[:x1], b[:y1], c[:z1]``: screen here, then ``align_batch``
+    (any path) the prefixes of the hits. ``"face"`` and ``"any"`` need a cube
+    the factored f16-class helix scores with max_lc <= 256 and max_lb <= 2048;
+    anything else raises ``TsaError(TSA_ERANGE)``."""
+    mode = _end_mode(end, "score_batch_ends")
+    p = params or TsaParams.default()
+    if seqs is None:
+        seqs, offsets = pack_batch(triples)
+    seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = (len(offsets) - 1) // 3
+    sc = np.zeros(max(n, 1), dtype=np.int32)
+    en = np.zeros(max(3 * n, 1), dtype=np.int32)
+    rc = _lib.tsa_score_batch_ends(_ptr(seqs, ctypes.c_uint8), _ptr(offsets, ctypes.c_int64), n, ctypes.byref(p),
+                                   mode, _ptr(sc, ctypes.c_int32), _ptr(en, ctypes.c_int32), device)
+    _check(rc, "tsa_score_batch_ends")
+    return [(s, tuple(e)) for s, e in zip(sc[:n].tolist(), en[:3 * n].reshape(-1, 3).tolist())]
+
+
+def score_ends_workspace_size(n: int, max_la: int, max_lb: int, max_lc: int, params: Optional[TsaParams] = None,
+                              end: str | int = "any") -> int:
+    """Bytes of workspace ``score_batch_ends_async`` needs (tsa_score_ends_workspace_size)."""
+    p = params or TsaParams.default()
+    sz = ctypes.c_size_t(0)
+    _check(_lib.tsa_score_ends_workspace_size(n, max_la, max_lb, max_lc, ctypes.byref(p),
+                                              _end_mode(end, "score_ends_workspace_size"), ctypes.byref(sz)),
+           "tsa_score_ends_workspace_size")
+    return int(sz.value)
+
+
+def score_batch_ends_async(d_seqs_ptr: int, d_offsets_ptr: int, n: int, max_la: int, max_lb: int, max_lc: int,
+                           d_scores_ptr: int, d_ends_ptr: int, d_ws_ptr: int, ws_bytes: int, stream_ptr: int = 0,
+                           params: Optional[TsaParams] = None, end: str | int = "any") -> None:
+    """Device-resident ``score_batch_ends`` (tsa_score_batch_ends_async): raw
+    device addresses, results (n scores, 3n ends, int32) stay on the device."""
+    p = params or TsaParams.default()
+    rc = _lib.tsa_score_batch_ends_async(ctypes.c_void_p(d_seqs_ptr), ctypes.c_void_p(d_offsets_ptr), n, max_la,
+                                         max_lb, max_lc, ctypes.byref(p), _end_mode(end, "score_batch_ends_async"),
+                                         ctypes.c_void_p(d_scores_ptr), ctypes.c_void_p(d_ends_ptr),
+                                         ctypes.c_void_p(d_ws_ptr), ctypes.c_size_t(ws_bytes),
+                                         ctypes.c_void_p(stream_ptr))
+    _check(rc, "tsa_score_batch_ends_async")
+
+
+def describe_score_ends_plan(n: int, max_la: int, max_lb: int, max_lc: int, params: Optional[TsaParams] = None,
+                             end: str | int = "any") -> str:
+    """The plan ``score_batch_ends`` runs (tsa_describe_score_ends_plan; host-only):
+    the helix plan with ``ends=face`` or ``ends=any``, or ``describe_plan``'s text
+    for the corner. Raises ``TsaError`` with the code the scoring call would return."""
+    p = params or TsaParams.default()
+    buf = ctypes.create_string_buffer(512)
+    _check(_lib.tsa_describe_score_ends_plan(n, max_la, max_lb, max_lc, ctypes.byref(p),
+                                             _end_mode(end, "describe_score_ends_plan"), buf, len(buf)),
+           "tsa_describe_score_ends_plan")
+    return buf.value.decode()
 
 
 def penalty_table(params: Optional[TsaParams] = None):

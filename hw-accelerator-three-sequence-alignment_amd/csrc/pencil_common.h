@@ -81,8 +81,9 @@ struct PencilArgs {
   uint32_t i_bias;              // bias in both halves
   uint32_t i_lam, i_cP, i_dO;   // 8 lam, 8 (GO + MISMATCH + lam), 8 (GO - GE): both halves, 32-bit subtrahends
   int32_t dm8, d0_8, d1_8;      // 8 (match - mismatch), 8 d0, 8 d1 (weights 8 w / code)
+  // End search (the END instantiations, end_class): candidates on the end faces only
+  int32_t end_face;
 };
-
 
 // Literal RTL arithmetic (literal_kernel.hip, the lap kernel's LIT form):
 // constants as int16 values shifted left by sh = 16 - SCORE_BITS, both halves,
@@ -503,6 +504,84 @@ __device__ __forceinline__ void cell_messages_vi(
   }
 }
 
+// ---------------------------------------------------------------------------
+// End search of the helix (pencil_kernel END). A position keeps
+// one 32-bit key per half,
+//   [31:20] score + 2048   [19:8] 4095 - (x - 1)   [7:0] 255 - lap,
+// folded with an unsigned max over the real cells it computes: the largest key
+// is the best score at the smallest x, then (the wave, hence y mod NW, being
+// fixed) the smallest y. z and the wave join the key after the loop
+// (end_key64). Any order of folding gives the same key. The host admits only
+// shapes whose fields fit (pencil_ends_admit): x - 1 <= 4095, lap <= 255, and
+// every score within +-2048 by use_f16.
+//
+// At one step the positions of a wave fall into two classes, each with
+// wave-uniform terms: those that have wrapped (k <= xpos0) compute x - 1 =
+// xpos0 - k of row lap0, the others x - 1 = xpos0 + P - k of row lap0 - 1. So
+// is the potential lam (x + y + z) of the V-space forms: x + z = xq + 2 for the
+// whole class. EndClass holds, for cells x - 1 = xq - k of row `row` (0-based):
+//   start, width  real candidates are the positions start <= k < start + width
+//                 (x <= la, the row started and <= lb; face mode: x = la or
+//                 y = lb); widthz the same for the position z = lc, whose
+//                 cells are all on a face
+//   add           what turns a half's value into its key but for k << 8
+constexpr uint32_t END_XBITS = 12, END_XMASK = (1u << END_XBITS) - 1u, END_LAPBITS = 8, END_LAPMASK = 255u;
+struct EndClass {
+  uint32_t start, width, widthz, add;
+};
+// VI: a half is bias + 8 V, so (half - bias - 8 lam q) << 17 puts score at bit 20
+template <bool VI>
+__device__ __forceinline__ EndClass end_class(const PencilArgs &pa, int32_t xq, int32_t lap, int32_t row,
+                                              int32_t la, int32_t lb) {
+  const bool ok = lap >= 0 && row < lb;
+  const int32_t lim = ok ? la : 0;
+  const int32_t q = xq + row + 3;  // x + y + z of the class
+  const int32_t top = VI ? (16384 - pa.bias - 8 * pa.lam * q) : (2048 - pa.lam * q);
+  // Each term goes to a VGPR by a v_mov of its own. Left to the compiler, the
+  // scalar chain behind them (xpos0, lap0) has so many vector users that it
+  // is moved to the VALU as a whole, and the step's scalar operands with it.
+  auto to_v = [](uint32_t s) -> uint32_t {
+    uint32_t v;
+    asm("v_mov_b32 %0, %1" : "=v"(v) : "s"(s));
+    return v;
+  };
+  EndClass e;
+  e.start = to_v((uint32_t)(xq - lim + 1));
+  e.widthz = to_v((uint32_t)lim);
+  e.width = to_v(pa.end_face ? (uint32_t)(!ok ? 0 : row + 1 == lb ? la : 1) : (uint32_t)lim);
+  e.add = to_v(((uint32_t)top << (VI ? 17 : 20)) + ((uint32_t)((int32_t)END_XMASK - xq) << END_LAPBITS) +
+               (uint32_t)((int32_t)END_LAPMASK - lap));
+  return e;
+}
+// Fold register `best` (positions k0 and k0 + 64 M in its halves) into their keys.
+template <int M, bool VI, bool FACE>
+__device__ __forceinline__ void end_fold(uint32_t best, uint32_t k0, uint32_t kz, const EndClass &eA,
+                                         const EndClass &eB, uint32_t &key_lo, uint32_t &key_hi) {
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const uint32_t k = k0 + 64u * M * h;
+    uint32_t hv;  // the half's value at the score field (modulo 2^32: the sum below is exact)
+    if constexpr (VI) {
+      hv = (h ? best >> 16 : best) << 17;
+    } else {
+      const _Float16 f = __builtin_bit_cast(_Float16, (uint16_t)(h ? best >> 16 : best));
+      hv = (uint32_t)(int32_t)(float)f << 20;
+    }
+    const uint32_t wa = FACE ? (k == kz ? eA.widthz : eA.width) : eA.width;
+    const uint32_t wb = FACE ? (k == kz ? eB.widthz : eB.width) : eB.width;
+    const bool inA = k - eA.start < wa, inB = k - eB.start < wb;  // unsigned: start <= k < start + width
+    const uint32_t cand = hv + (inA ? eA.add : eB.add) + (k << END_LAPBITS);
+    uint32_t &key = h ? key_hi : key_lo;
+    key = max(key, (inA || inB) ? cand : 0u);
+  }
+}
+__device__ __forceinline__ uint64_t umax64(uint64_t a, uint64_t b) { return a > b ? a : b; }
+// A position's key with its wave w and position k: {score : ~(x-1)} : ~y : ~z
+__device__ __forceinline__ uint64_t end_key64(uint32_t key, uint32_t w, int NW, uint32_t k) {
+  const uint32_t y = (END_LAPMASK - (key & END_LAPMASK)) * (uint32_t)NW + w + 1u, z = k + 1u;
+  return ((uint64_t)(key >> END_LAPBITS) << 32) | ((0xFFFFu - y) << 16) | (0xFFFFu - z);
+}
+
 // Shift a packed per-position value one position up the helix (k <- k-1).
 // With k = 64M*h + M*lane + i, register i >= 1 takes register i-1 of the same
 // lane (a rename, no instruction); register 0 takes register M-1 of lane-1
@@ -588,9 +667,10 @@ __device__ __forceinline__ void pos_split(int32_t k, int32_t &l, int32_t &i, int
 // The step lambdas are left to the regular inliner for M <= 2 (an early forced
 // inline costs ~7 % there); for M >= 4 the inliner gives up on their size and
 // the captured state would spill to scratch, so those calls are forced inline.
+// So are the end search's (END): the fold makes the step too large as well.
 #define TSA_INLINE_IF_WIDE(call)                 \
   do {                                           \
-    if constexpr (M >= 4) {                      \
+    if constexpr (M >= 4 || END) {               \
       [[clang::always_inline]] call;             \
     } else {                                     \
       call;                                      \

@@ -42,6 +42,18 @@ int pencil_launch_batch(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t
                         const Range &bound, int32_t *d_scores, void *d_ws, size_t ws_bytes,
                         hipStream_t stream, LapPolicy lap, int32_t **d_err,
                         const CheckLimits *chk = nullptr);
+// The end search of the helix (tsa_score_batch_ends under face and any): the
+// admission (TSA_OK, TSA_ERANGE, or TSA_EINVAL for an override that rules the
+// plan out), the ring it needs, its plan as text, and the launch of up to
+// 65535 triples: d_scores[i] the best MAX7 over the real cells of the mode,
+// d_ends[3i..3i+2] the cell (smallest x, then y, then z among equals).
+int pencil_ends_admit(int32_t max_la, int32_t max_lb, int32_t max_lc, const KParams &kp, const Range &bound);
+size_t pencil_ends_workspace_bytes(int32_t n, int32_t max_la, int32_t max_lc);
+void pencil_describe_ends(int32_t max_la, int32_t max_lb, int32_t max_lc, const KParams &kp, const Range &bound,
+                          bool face, char *buf, size_t len);
+int pencil_launch_ends(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, int32_t max_la,
+                       int32_t max_lb, int32_t max_lc, const KParams &kp, const Range &bound, bool face,
+                       int32_t *d_scores, int32_t *d_ends, void *d_ws, size_t ws_bytes, hipStream_t stream);
 // The checked lap kernel (TSA_KERNEL_CHECKED) can run this batch: the lap
 // schedule is chosen for it (int16 arithmetic).
 bool pencil_checked_plan(int32_t n, int32_t max_la, int32_t max_lb, int32_t max_lc,

@@ -272,11 +272,12 @@ static bool helix_two(int32_t max_lc) {
   if (override_int("pencil_two", &v)) return v != 0 && max_lc <= 64;  // plan override (A/B)
   return max_lc <= 64;
 }
-static PencilGeom pencil_geom(int32_t max_la, int32_t max_lc) {
+// no_two: the end search's geometry (a wave's two halves are one triple's)
+static PencilGeom pencil_geom(int32_t max_la, int32_t max_lc, bool no_two = false) {
   PencilGeom g;
   g.M = pencil_pairs(max_lc);
   // >= 64 > NW + helix_pd + STORE_SLACK: ring lag
-  g.two = helix_two(max_lc);
+  g.two = !no_two && helix_two(max_lc);
   g.P = std::max(max_la, g.two ? 64 : 128 * g.M);
   g.P = (g.P + g.M - 1) / g.M * g.M;  // even for M = 2: the x = 1 register is PH ^ (w & 1)
   if (g.M == 2 && !g.two && TSA_EV_STATIC) g.P = (g.P + 3) / 4 * 4;  // TSA_EV_STATIC
@@ -397,6 +398,18 @@ bool pencil_shape_supported(int32_t max_la, int32_t max_lb, int32_t max_lc) {
   return pencil_shape_ok(max_la, max_lb, max_lc);
 }
 
+// The end search's per-lane state (pencil_kernel END): the running key of each
+// position (v[h][i]: half h of register i) and the lane's first position. Empty
+// unless END: as plain locals the step lambda captures them, and unused they
+// still cost every other instantiation a VGPR.
+template <int M, bool END>
+struct EndKeys {
+  uint32_t v[2][M];
+  uint32_t kl;
+};
+template <int M>
+struct EndKeys<M, false> {};
+
 // ---------------------------------------------------------------------------
 // Helix kernel: one workgroup per triple (grid-stride over the batch).
 //   LDS: xr  [NW-1][2][M][64][16]  wave w -> w+1 records {Iy, Ixy, Iyz, best}
@@ -411,7 +424,12 @@ bool pencil_shape_supported(int32_t max_la, int32_t max_lb, int32_t max_lc) {
 // VI: the V-space cell on integer bit patterns (cell_messages_vi): every half
 // holds bias + 8 V, the symbol codes are 1 << s, the per-row terms integer
 // weights. Records, ring, z-shifts and injections move bits and do not change.
-template <int M, int NW, bool F16, bool SOP, bool TWO, bool VS, bool VI = false>
+// END: the end-free score (tsa_score_batch_ends): every step folds the real
+// cells' MAX7 into one key per position and half (end_fold, pencil_common.h);
+// the largest key gives scores[tri] and ends[3 tri ..] = (x1, y1, z1), and the
+// corner's fin capture drops out. pa.end_face restricts the candidates
+// to the three end faces (wave-uniform, tested once per step).
+template <int M, int NW, bool F16, bool SOP, bool TWO, bool VS, bool VI = false, bool END = false>
 __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restrict__ seqs,
                                                          const int64_t *__restrict__ offs,
                                                          int32_t n, int32_t P, int32_t R,
@@ -419,7 +437,7 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
                                                          int64_t ring_stride,
                                                          uint8_t *__restrict__ ring_base,
                                                          int32_t *__restrict__ scores,
-                                                         PencilArgs pa) {
+                                                         PencilArgs pa, int32_t *__restrict__ ends) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   constexpr int PAIR_BYTES = 64 * REC_BYTES;  // one pair's record, 1 KiB
   constexpr int SLOT_BYTES = M * PAIR_BYTES;
@@ -440,6 +458,7 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
   static_assert(!VS || (F16 && M <= 2), "V-space: the f16 helix with the four-step loop");
   static_assert(!VI || (VS && M == 2 && !TWO && helix_skew(M) == 2 && !TSA_H_TAB && !TSA_SHIFTED_REC && !TSA_PREINJ),
                 "integer patterns: the V-space M = 2 helix at skew 2");
+  static_assert(!END || (F16 && !TWO && M <= 2), "end search: the f16-class helix, one triple per workgroup");
   constexpr uint32_t SYMC = VI ? 1u : SYM0;  // symbol codes SYMC << s
   // f16 bits of an integer (|v| <= 2048: exact), in both halves; VI: bias + 8 v
   auto h_bits = [&](int32_t v) -> uint32_t {
@@ -589,6 +608,13 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
       shIxz[0][i] = shIxz[1][i] = pa.f_pair;
       svIxy[i] = svIyz[i] = pa.f_pair;
       svM[0][i] = svM[1][i] = VI ? pa.i_bias : 0u;  // (VI: f_single, f_pair are the bias too)
+    }
+    // END: the running key of each position (ek.v[h][i]: half h of register i)
+    EndKeys<M, END> ek;
+    if constexpr (END) {
+#pragma unroll
+      for (int i = 0; i < M; ++i) ek.v[0][i] = ek.v[1][i] = 0u;
+      ek.kl = (uint32_t)(M * lane);
     }
     // position-0 bookkeeping (wave-uniform): u0 = t - w
     int32_t xpos0 = (P - ((HSK * w) % P)) % P;  // (t - HSK w) mod P at t = 0
@@ -965,7 +991,8 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
       if constexpr (TSA_SETPRIO) __builtin_amdgcn_s_setprio(1);
       // ---- the final cell (src/TriAlign_1cyc.v:141-142,342-345) is in wave w_f's
       // last step; it is read back after the loop
-      if constexpr (TWO) {  // two final cells, possibly at different steps
+      if constexpr (END) {  // no corner capture: the keys are folded after the record is sent
+      } else if constexpr (TWO) {  // two final cells, possibly at different steps
         if (t == t_f && w == w_f) fin[lane] = oBest[0];
         if (t == t_f1 && w == w_f1) fin[64 + lane] = oBest[0];
       } else if constexpr (VS) {  // the four-step loop runs past T: the final step is tested
@@ -1050,6 +1077,24 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
             ring_st16(rs_ring63, own, row + 10, oIyz[M - 1]);
             ring_st16(rs_ring63, own, row + 14, oBest[M - 1]);
           }
+        }
+      }
+      // ---- END: fold this step's real cells into the positions' keys. Position k
+      // holds x - 1 = xpos0 - k of row lap0 NW + w + 1 once it has wrapped
+      // (k <= xpos0: class A) and x - 1 = xpos0 + P - k of the row NW above
+      // otherwise (class B); each class's terms are wave-uniform (end_class).
+      // The last wave's unstarted positions were overwritten above: not real.
+      if constexpr (END) {
+        const EndClass eA = end_class<VI>(pa, xpos0, lap0, lap0 * NW + w, la, lb);
+        const EndClass eB = end_class<VI>(pa, xpos0 + P, lap0 - 1, (lap0 - 1) * NW + w, la, lb);
+        if (pa.end_face) {
+#pragma unroll
+          for (int i = 0; i < M; ++i)
+            end_fold<M, VI, true>(oBest[i], ek.kl + i, (uint32_t)(lc - 1), eA, eB, ek.v[0][i], ek.v[1][i]);
+        } else {
+#pragma unroll
+          for (int i = 0; i < M; ++i)
+            end_fold<M, VI, false>(oBest[i], ek.kl + i, (uint32_t)(lc - 1), eA, eB, ek.v[0][i], ek.v[1][i]);
         }
       }
       // ---- advance the systolic registers
@@ -1327,9 +1372,39 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
     } else {
       TSA_INLINE_IF_WIDE(run_wave(std::false_type{}));
     }
+    if constexpr (END) {
+      // z and the wave's row join the key here: {score | ~(x-1)} : ~y : ~z, so the
+      // largest is the best score at the smallest x, then y, then z. Positions
+      // past lc (padding in z) never enter. A wave reduce, then fin[2 w ..].
+      uint64_t bk = 0;
+#pragma unroll
+      for (int i = 0; i < M; ++i)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int32_t k = M * lane + i + 64 * M * h;
+          const uint32_t key = ek.v[h][i];
+          if (k < lc && key != 0u) bk = umax64(bk, end_key64(key, (uint32_t)w, NW, (uint32_t)k));
+        }
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) bk = umax64(bk, (uint64_t)__shfl_xor((unsigned long long)bk, o, 64));
+      if (lane == 0) {
+        fin[2 * w] = (uint32_t)bk;
+        fin[2 * w + 1] = (uint32_t)(bk >> 32);
+      }
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if constexpr (END) {
+      if (threadIdx.x == 0) {
+        uint64_t bk = 0;
+        for (int j = 0; j < NW; ++j) bk = umax64(bk, ((uint64_t)fin[2 * j + 1] << 32) | fin[2 * j]);
+        const uint32_t top = (uint32_t)(bk >> 32);  // {score + 2048 : 4095 - (x - 1)}
+        scores[tri] = (int32_t)(top >> END_XBITS) - 2048;
+        ends[3 * (int64_t)tri] = (int32_t)(END_XMASK - (top & END_XMASK)) + 1;
+        ends[3 * (int64_t)tri + 1] = (int32_t)(0xFFFFu - (((uint32_t)bk >> 16) & 0xFFFFu));
+        ends[3 * (int64_t)tri + 2] = (int32_t)(0xFFFFu - ((uint32_t)bk & 0xFFFFu));
+      }
+    } else if (threadIdx.x == 0) {
       auto decode = [&](uint16_t hb) -> int32_t {
         if constexpr (VI) return ((int32_t)hb - pa.bias) / 8;  // u = bias + 8 V
         return F16 ? (int32_t)(float)__builtin_bit_cast(_Float16, hb) : (int32_t)(int16_t)hb;
@@ -1536,10 +1611,11 @@ static bool lap_vs_ok(const KParams &kp, const Range &r, int32_t max_la, int32_t
   return r.lo - slack >= -2048 && hi <= 2048 && (int64_t)GO + GE + kp.mismatch <= 2048;
 }
 
+// d_ends: the end search's instantiation (END) of the same arithmetic
 template <int M, int NW, bool F16, bool SOP>
 static int launch_m(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n,
                     int32_t max_lb, const PencilGeom &g, int32_t *d_scores, void *d_ws,
-                    const PencilArgs &pa, hipStream_t stream) {
+                    const PencilArgs &pa, hipStream_t stream, int32_t *d_ends = nullptr) {
   constexpr bool VSOK = F16 && M <= 2;  // V-space instantiations
   const bool vs = VSOK && pa.lam != 0;
   const int32_t lds_a = 4 * (g.P + 128 * M + A_PAD), lds_b = 4 * ((max_lb + 3) & ~3);
@@ -1551,12 +1627,24 @@ static int launch_m(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n,
   if constexpr (VSOK && M == 2 && VI_BUILT) {  // the integer-pattern cell (use_vi set the bias)
     if (vs && pa.bias != 0) kfn = pencil_kernel<M, NW, F16, SOP, false, VSOK, true>;
   }
+  if (d_ends) {
+    if constexpr (VSOK) {
+      if (two) return TSA_EINVAL;
+      kfn = vs ? pencil_kernel<M, NW, F16, SOP, false, VSOK, false, true>
+               : pencil_kernel<M, NW, F16, SOP, false, false, false, true>;
+      if constexpr (M == 2 && VI_BUILT) {
+        if (vs && pa.bias != 0) kfn = pencil_kernel<M, NW, F16, SOP, false, VSOK, true, true>;
+      }
+    } else {
+      return TSA_ERANGE;  // no end search in the int16 form or beyond M = 2
+    }
+  }
   if (lds > LDS_MAX) return TSA_EINVAL;
   const int32_t units = two ? (n + 1) / 2 : n;
   const int grid = units < 65535 ? units : 65535;
   return launch_with_lds((const void *)kfn, lds, [&] {
            hipLaunchKernelGGL(kfn, dim3(grid), dim3(64 * NW), lds, stream, d_seqs, d_offsets, n, g.P, g.R, lds_a,
-                              lds_b, g.ring_bytes_per_triple, (uint8_t *)d_ws, d_scores, pa);
+                              lds_b, g.ring_bytes_per_triple, (uint8_t *)d_ws, d_scores, pa, d_ends);
          }) == hipSuccess
              ? TSA_OK
              : TSA_EDEVICE;
@@ -1581,6 +1669,62 @@ void pencil_describe(int32_t n, int32_t max_la, int32_t max_lb, int32_t max_lc, 
   const bool vi = !checked && use_vi(kp, bound, max_la, max_lb, max_lc) != 0;  // on integer patterns
   snprintf(buf, len, "pencil helix %s %s M=%d NW=%d P=%d%s est=%.0fus", arith, s3, g.M, helix_nw(g.M), g.P,
            g.two ? " two" : vi ? " int" : "", helix_est(n, max_la, max_lb, max_lc));
+}
+
+// The end search (tsa_score_batch_ends, face and any): always the helix, one
+// triple per workgroup, in f16-class arithmetic. TSA_OK when the request is
+// admitted: LC <= 256, and the key's fields hold every real cell (end_fold: x - 1
+// in 12 bits, the lap in 8; the score by use_f16). TSA_ERANGE otherwise;
+// TSA_EINVAL for a set pencil_mode other than helix, and for pencil_arith =
+// f16vi where the integer cell is not admitted (as pencil_launch_batch).
+int pencil_ends_admit(int32_t max_la, int32_t max_lb, int32_t max_lc, const KParams &kp, const Range &bound) {
+  char mode[16] = "";
+  if (override_str("pencil_mode", mode, sizeof mode) && strcmp(mode, "helix")) return TSA_EINVAL;
+  if (!pencil_shape_ok(max_la, max_lb, max_lc) || !use_f16(kp, bound) || pencil_pairs(max_lc) > 2)
+    return TSA_ERANGE;
+  if (max_la - 1 > (int32_t)END_XMASK || (max_lb - 1) / helix_nw(pencil_pairs(max_lc)) > (int32_t)END_LAPMASK)
+    return TSA_ERANGE;
+  const PencilGeom g = pencil_geom(max_la, max_lc, true);
+  const bool vs = use_vs(kp, bound, max_la, max_lb, max_lc);
+  if (helix_lds(g.M, helix_nw(g.M), g.P, max_lb, vs) > LDS_MAX) return TSA_ERANGE;
+  if (arith_override("f16vi") && use_vi(kp, bound, max_la, max_lb, max_lc) == 0) return TSA_EINVAL;
+  return TSA_OK;
+}
+
+size_t pencil_ends_workspace_bytes(int32_t n, int32_t max_la, int32_t max_lc) {
+  return (size_t)std::min<int32_t>(n, 65535) * (size_t)pencil_geom(max_la, max_lc, true).ring_bytes_per_triple;
+}
+
+// pencil_describe's helix text with the end mode in place of the estimate
+// (helix_est is the plain score's)
+void pencil_describe_ends(int32_t max_la, int32_t max_lb, int32_t max_lc, const KParams &kp, const Range &bound,
+                          bool face, char *buf, size_t len) {
+  const PencilGeom g = pencil_geom(max_la, max_lc, true);
+  const bool vs = use_vs(kp, bound, max_la, max_lb, max_lc);
+  const bool vi = use_vi(kp, bound, max_la, max_lb, max_lc) != 0;
+  snprintf(buf, len, "pencil helix %s %s M=%d NW=%d P=%d%s ends=%s", vs ? "f16v" : "f16",
+           kp.s3_mode == TSA_S3_SOP ? "sop" : "rtl", g.M, helix_nw(g.M), g.P, vi ? " int" : "", face ? "face" : "any");
+}
+
+int pencil_launch_ends(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, int32_t max_la,
+                       int32_t max_lb, int32_t max_lc, const KParams &kp, const Range &bound, bool face,
+                       int32_t *d_scores, int32_t *d_ends, void *d_ws, size_t ws_bytes, hipStream_t stream) {
+  if (n <= 0) return TSA_OK;
+  if (!d_ends) return TSA_EINVAL;
+  const int rc = pencil_ends_admit(max_la, max_lb, max_lc, kp, bound);
+  if (rc) return rc;
+  if (n > 65535) return TSA_EINVAL;  // the callers chunk
+  const bool sop = kp.s3_mode == TSA_S3_SOP;
+  PencilArgs pa = make_args(kp, true, use_vs(kp, bound, max_la, max_lb, max_lc),
+                            use_vi(kp, bound, max_la, max_lb, max_lc));
+  pa.end_face = face ? 1 : 0;
+  const PencilGeom g = pencil_geom(max_la, max_lc, true);
+  if (ws_bytes < (size_t)n * (size_t)g.ring_bytes_per_triple) return TSA_ENOMEM;
+  if (g.M == 1)
+    return sop ? launch_m<1, 8, true, true>(d_seqs, d_offsets, n, max_lb, g, d_scores, d_ws, pa, stream, d_ends)
+               : launch_m<1, 8, true, false>(d_seqs, d_offsets, n, max_lb, g, d_scores, d_ws, pa, stream, d_ends);
+  return sop ? launch_m<2, 8, true, true>(d_seqs, d_offsets, n, max_lb, g, d_scores, d_ws, pa, stream, d_ends)
+             : launch_m<2, 8, true, false>(d_seqs, d_offsets, n, max_lb, g, d_scores, d_ws, pa, stream, d_ends);
 }
 
 int pencil_launch_batch(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n,

@@ -2,7 +2,7 @@
 // "TriAlign Score: <n>" (src/TriAlign_tb.sv:339-341).
 //   tsa A.dat B.dat C.dat [--kernel auto|plane|pencil] [--device N]
 //       [--s3 rtl|sop] [--bits B] [--match M --mismatch X --go O --ge E]
-//       [--states] [--align [--end corner|face|any]]
+//       [--states] [--align [--end corner|face|any]] [--score-end face|any]
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -17,13 +17,16 @@ static int usage() {
           "           [--align]   (also print the optimal alignment; tsa_align_gpu)\n"
           "           [--end corner|face|any]   (with --align: where the path may end; face and any\n"
           "                                      go through tsa_align_batch_ends and print the end)\n"
+          "           [--score-end face|any]   (without --align: the end-free score and its end cell,\n"
+          "                                     tsa_score_batch_ends; no alignment is traced. Its plan is\n"
+          "                                     always the helix: with --kernel or --states a usage error)\n"
           "A/B/C: dat files (one symbol 0..4 per line) or FASTA (A=0 T=1 C=2 G=3 N=4)\n");
   return 2;
 }
 
 int main(int argc, char **argv) {
   const char *files[3];
-  int nf = 0, device = 0, kernel = TSA_KERNEL_AUTO, states = 0, align = 0, end = TSA_END_CORNER;
+  int nf = 0, device = 0, kernel = TSA_KERNEL_AUTO, kernel_set = 0, states = 0, align = 0, end = TSA_END_CORNER, score_end = TSA_END_CORNER;
   tsa_params p;
   tsa_default_params(&p);
   for (int i = 1; i < argc; ++i) {
@@ -32,6 +35,7 @@ int main(int argc, char **argv) {
     if (!strcmp(a, "--kernel")) {
       const char *v = next();
       if (!v) return usage();
+      kernel_set = 1;
       kernel = !strcmp(v, "plane") ? TSA_KERNEL_PLANE : !strcmp(v, "pencil") ? TSA_KERNEL_PENCIL : TSA_KERNEL_AUTO;
     } else if (!strcmp(a, "--device")) { const char *v = next(); if (!v) return usage(); device = atoi(v); }
     else if (!strcmp(a, "--s3")) { const char *v = next(); if (!v) return usage(); p.s3_mode = !strcmp(v, "sop") ? TSA_S3_SOP : TSA_S3_RTL; }
@@ -50,11 +54,19 @@ int main(int argc, char **argv) {
       else if (!strcmp(v, "any")) end = TSA_END_ANY;
       else return usage();
     }
+    else if (!strcmp(a, "--score-end")) {
+      const char *v = next();
+      if (!v) return usage();
+      if (!strcmp(v, "face")) score_end = TSA_END_FACE;
+      else if (!strcmp(v, "any")) score_end = TSA_END_ANY;
+      else return usage();
+    }
     else if (a[0] == '-' && a[1] == '-') return usage();
     else if (nf < 3) files[nf++] = a;
     else return usage();
   }
   if (nf != 3 || (end != TSA_END_CORNER && !align)) return usage();
+  if (score_end != TSA_END_CORNER && (align || states || kernel_set)) return usage();
   uint8_t *s[3];
   int64_t n[3];
   for (int k = 0; k < 3; ++k) {
@@ -62,6 +74,20 @@ int main(int argc, char **argv) {
     if (n[k] < 0) { fprintf(stderr, "tsa: cannot read %s\n", files[k]); return 1; }
   }
   int32_t score = 0, fin[7];
+  if (score_end != TSA_END_CORNER) {  // a batch of one: the three sequences back to back
+    const int64_t cap = n[0] + n[1] + n[2];
+    uint8_t *seqs = (uint8_t *)malloc((size_t)cap);
+    const int64_t off[4] = {0, n[0], n[0] + n[1], cap};
+    int32_t en[3] = {0, 0, 0};
+    if (seqs)
+      for (int k = 0; k < 3; ++k) memcpy(seqs + off[k], s[k], (size_t)n[k]);
+    const int rc = seqs ? tsa_score_batch_ends(seqs, off, 1, &p, score_end, &score, en, device) : TSA_ENOMEM;
+    free(seqs);
+    if (rc) { fprintf(stderr, "tsa: %s (%d)\n", tsa_strerror(rc), rc); return 1; }
+    printf("TriAlign Score:        \t%d\n", score);
+    printf("end (x1,y1,z1) = (%d,%d,%d)\n", en[0], en[1], en[2]);
+    return 0;
+  }
   int rc = tsa_score_gpu_ex(s[0], (int32_t)n[0], s[1], (int32_t)n[1], s[2], (int32_t)n[2], &p,
                             states ? TSA_KERNEL_PLANE : kernel, &score, states ? fin : nullptr, device);
   if (rc) { fprintf(stderr, "tsa: %s (%d)\n", tsa_strerror(rc), rc); return 1; }

@@ -354,7 +354,8 @@ int tsa_align_batch_grid(const uint8_t *seqs, const int64_t *offsets, int32_t n,
  *
  * Not covered: the strip and grid paths, the plane sweep, tsa_align_gpu, a
  * device-resident form (tsa_align_rows_async works on uploaded results as it
- * is), and an end-free score-only mode of the helix and lap scorers. */
+ * is). The end-free score without a path is tsa_score_batch_ends below; the
+ * prefixes it returns can be aligned on every traceback path. */
 #define TSA_END_CORNER 0
 #define TSA_END_FACE 1
 #define TSA_END_ANY 2
@@ -362,6 +363,61 @@ int tsa_align_batch_ends(const uint8_t *seqs, const int64_t *offsets, int32_t n,
                          const tsa_params *p, int32_t end_mode, int32_t *scores,
                          uint8_t *moves, int32_t *n_moves, int32_t *starts,
                          int32_t *ends, int32_t device);
+
+/* End-free scores without a path: scores[i] and ends[3i..3i+2] exactly as
+ * tsa_align_batch_ends defines them (the same candidates per end_mode, the
+ * same MAX7, the same tie rule; no state index), computed by the factored
+ * helix scorer as it sweeps, with no memory per cell. The recurrence is
+ * causal, so the free-end alignment is the corner alignment of the prefixes
+ * a[0..x1), b[0..y1), c[0..z1): screen a batch here, then trace back only the
+ * hits with any traceback entry point (tsa_align_batch, _grid, _async ...).
+ *
+ * Layouts, validation order and thread safety are tsa_score_batch's and
+ * tsa_score_batch_async's (on the async call the symbols are the caller's job,
+ * and it only queues work). Errors, in this order and before any device work:
+ * TSA_EINVAL for a null pointer (ends included), bad offsets, symbols or
+ * parameters, or an end_mode outside 0..2; TSA_OK for n == 0; TSA_ERANGE for a
+ * request the plan below does not admit; TSA_ENODEV with no HIP device or a
+ * device index out of range. There is no CPU fallback. The synchronous call
+ * runs chunks of at most 65535 triples whose workspace stays under the cap of
+ * tsa_score_batch, one launch each.
+ *
+ * TSA_END_CORNER runs tsa_score_batch's own plan (TSA_KERNEL_AUTO; on the
+ * async call tsa_score_batch_async's, with tsa_batch_workspace_size's
+ * workspace) and fills ends with the lengths. Under TSA_END_FACE and
+ * TSA_END_ANY the plan is always the helix with one triple per workgroup --
+ * never the lap schedule, never two triples per wave (pencil_two is ignored) --
+ * and a request is admitted exactly when tsa_score_batch would score
+ * (max_la, max_lb, max_lc) with the factored form in f16-class arithmetic
+ * (plain f16, V-space float or V-space integer patterns, as the score plan
+ * picks), max_lc <= 256 and max_lb <= 2048 (the end search's key holds the row
+ * in 8 bits of laps). The int16 form, literal-only parameter sets
+ * (gap_open < gap_extend), pencil_arith = i16 and larger cubes are TSA_ERANGE;
+ * a set pencil_mode other than helix is TSA_EINVAL. The workspace is the helix
+ * ring of that geometry (tsa_score_ends_workspace_size; it may hold anything
+ * on entry); tsa_kernel_launch_count rises by one per helix launch.
+ * tsa_describe_score_ends_plan returns the same codes on any host; its text is
+ * the helix plan's with " ends=face" or " ends=any" in place of the estimate,
+ * and tsa_describe_plan's (synchronous, TSA_KERNEL_AUTO) for the corner.
+ *
+ * Not covered: the literal helix and the lap kernels (so no end-free score
+ * where only the literal arithmetic is exact), cubes with max_lc > 256, and
+ * more than one device per call. */
+int tsa_score_batch_ends(const uint8_t *seqs, const int64_t *offsets, int32_t n,
+                         const tsa_params *p, int32_t end_mode, int32_t *scores,
+                         int32_t *ends /* 3n */, int32_t device);
+int tsa_score_ends_workspace_size(int32_t n, int32_t max_la, int32_t max_lb,
+                                  int32_t max_lc, const tsa_params *p,
+                                  int32_t end_mode, size_t *bytes);
+int tsa_score_batch_ends_async(const uint8_t *d_seqs, const int64_t *d_offsets,
+                               int32_t n, int32_t max_la, int32_t max_lb,
+                               int32_t max_lc, const tsa_params *p,
+                               int32_t end_mode, int32_t *d_scores,
+                               int32_t *d_ends, void *d_workspace,
+                               size_t workspace_bytes, void *stream);
+int tsa_describe_score_ends_plan(int32_t n, int32_t max_la, int32_t max_lb,
+                                 int32_t max_lc, const tsa_params *p,
+                                 int32_t end_mode, char *buf, size_t len);
 
 /* Device-resident traceback: tsa_align_batch on sequences that are already in
  * device memory, with results that stay there. d_* are device pointers on the

@@ -126,19 +126,68 @@ def vi_bias(max_la, max_lb, max_lc, match=1, mismatch=-1, go=2, ge=1, sop=False)
     return VI_LO - 8 * v_lo
 
 
+# The end search's key (pencil_common.h: end_fold): per position and half
+# {score + 2048 : 4095 - (x - 1) : 255 - lap} in 12 + 12 + 8 bits, folded with an
+# unsigned max; the wave and z join it in the final reduction (end_key64).
+M32 = 0xFFFFFFFF
+
+
+def end_key64(key, w, k):
+    y = (255 - (key & 255)) * NW + w + 1
+    return ((key >> 8) << 32) | ((0xFFFF - y) << 16) | (0xFFFF - (k + 1))
+
+
+def end_decode(key64):
+    """(score, (x, y, z)) of a reduced key."""
+    top = key64 >> 32
+    return (top >> 12) - 2048, (4095 - (top & 4095) + 1, 0xFFFF - ((key64 >> 16) & 0xFFFF), 0xFFFF - (key64 & 0xFFFF))
+
+
+def end_reduce(keys, lc):
+    """keys[w][i, lane, h] -> the workgroup's key: per position slot (the array),
+    then per wave, then across the waves, as the kernel reduces them."""
+    best = 0
+    for w in range(NW):
+        wave = 0
+        M = keys[w].shape[0]
+        for i in range(M):
+            for lane in range(64):
+                for h in range(2):
+                    k, key = 64 * M * h + M * lane + i, int(keys[w][i, lane, h])
+                    if k < lc and key:
+                        wave = max(wave, end_key64(key, w, k))
+        best = max(best, wave)
+    return best
+
+
 def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shifted=None, garbage_seed=None,
-            ring_garbage_seed=None, read_prev=False, int_bits=False, bias=None, events=None):
+            ring_garbage_seed=None, read_prev=False, int_bits=False, bias=None, events=None, end=None,
+            max_lens=None):
     """Scores of one workgroup's unit: one triple, or two (TWO mode: LC <= 64).
     Returns a list of scores (one per triple). `garbage_seed` starts the LDS
     record slots, `ring_garbage_seed` the global ring, with garbage (what an
     earlier launch left in the workspace): a ring row read before this unit
-    wrote it then spoils the score."""
+    wrote it then spoils the score.
+
+    end = "face" | "any": the END instantiation's fold (one triple): returns
+    [(score, (x1, y1, z1))]; a tuple of modes folds each in the same replay and
+    returns one such pair per mode. events["end_cands"], when the caller put a
+    list there, receives every folded candidate as (mode, w, i, lane, h, key),
+    and events["end_key"][mode] the reduced 64-bit key.
+
+    max_lens = (max_la, max_lb, max_lc): the batch's maxima, from which the
+    launch takes its geometry (M, P, the bias) -- a triple of a ragged batch
+    is replayed as the kernel runs it, inside a larger cube."""
     two = len(triples) == 2
+    end_modes = () if end is None else (end,) if isinstance(end, str) else tuple(end)
+    assert all(m in ("face", "any") for m in end_modes) and not (end_modes and two)
+    ekeys = {m: [None] * NW for m in end_modes}
     shifted = (vs and not read_prev) if shifted is None else shifted
     assert vs or not shifted
     assert not read_prev or (vs and not shifted)
     la_, lb_, lc_ = ([len(t[k]) for t in triples] for k in range(3))
-    max_la, max_lb, max_lc = max(la_), max(lb_), max(lc_)
+    max_la, max_lb, max_lc = (max(la_), max(lb_), max(lc_)) if max_lens is None else max_lens
+    assert max_la >= max(la_) and max_lb >= max(lb_) and max_lc >= max(lc_)
     M = 1 if max_lc <= 128 else 2
     assert not two or max_lc <= 64
     KS = 64 if two else 128 * M
@@ -388,6 +437,29 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
                 note("state", Sst)
                 note("term", Sst[None] - Pen[:, :, None, None, None])
                 note("msg", *msg)
+            for end_m in end_modes:  # the two classes' wave-uniform terms (end_class), then the fold (end_fold)
+                la1, lb1, lc1 = len(triples[0][0]), len(triples[0][1]), len(triples[0][2])
+
+                def end_class(xq, lap, row):
+                    ok = lap >= 0 and row < lb1
+                    lim = la1 if ok else 0
+                    q = xq + row + 3
+                    top = (16384 - bias - 8 * lam * q) if int_bits else (2048 - lam * q)
+                    width = (0 if not ok else la1 if row + 1 == lb1 else 1) if end_m == "face" else lim
+                    add = ((top << (17 if int_bits else 20)) + ((4095 - xq) << 8) + (255 - lap)) & M32
+                    return (xq - lim + 1) & M32, width, lim, add
+
+                cA = end_class(d["xpos0"], d["lap0"], d["lap0"] * NW + w)
+                cB = end_class(d["xpos0"] + P, d["lap0"] - 1, (d["lap0"] - 1) * NW + w)
+                zface = (kpos == lc1 - 1) if end_m == "face" else np.zeros(shape, bool)
+                inA = ((kpos - cA[0]) & M32) < np.where(zface, cA[2], cA[1])
+                inB = ((kpos - cB[0]) & M32) < np.where(zface, cB[2], cB[1])
+                hv = (np.asarray(best, np.int64) << (17 if int_bits else 20)) & M32
+                cand = np.where(inA | inB, (hv + np.where(inA, cA[3], cB[3]) + (kpos << 8)) & M32, 0)
+                ekeys[end_m][w] = cand if ekeys[end_m][w] is None else np.maximum(ekeys[end_m][w], cand)
+                if events.get("end_cands") is not None:
+                    events["end_cands"] += [(end_m, w, int(i), int(l), int(h), int(cand[i, l, h]))
+                                            for i, l, h in np.argwhere(inA | inB)]
             for j, (tf, wf, kf) in enumerate(zip(t_fs, w_fs, k_fs)):
                 if t == tf and w == wf:
                     pos = np.argwhere((kpos == kf) & (tri_of == j))[0]
@@ -433,6 +505,9 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
         for w in range(NW):
             xr[w, t & 3] = outs[w]
         ring[t % R] = outs[NW - 1]
+    if end_modes:
+        events["end_key"] = {m: end_reduce(ekeys[m], len(triples[0][2])) for m in end_modes}
+        return [end_decode(events["end_key"][m]) for m in end_modes]
     shifts = [lam * (len(a) + len(b) + len(c)) for (a, b, c) in (triples if two else triples[:1])]
     if int_bits:
         fin = [(f - bias) // 8 for f in fin]
