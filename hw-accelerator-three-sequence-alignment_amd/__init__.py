@@ -67,7 +67,7 @@ EXPORTS = (
     "tsa_kernel_launch_count", "tsa_align_batch", "tsa_describe_align_plan", "tsa_align_batch_lowmem",
     "tsa_align_batch_grid", "tsa_align_workspace_size", "tsa_align_batch_async", "tsa_align_rows_async",
     "tsa_align_batch_ends", "tsa_score_batch_ends", "tsa_score_ends_workspace_size",
-    "tsa_score_batch_ends_async", "tsa_describe_score_ends_plan",
+    "tsa_score_batch_ends_async", "tsa_describe_score_ends_plan", "tsa_align_batch_grid_ends",
 )
 
 # Plan overrides the library accepts (tsa_set_override; include/trialign.h).
@@ -165,6 +165,7 @@ def _load_lib() -> ctypes.CDLL:
     lib.tsa_align_batch_grid.argtypes = lib.tsa_align_batch.argtypes
     lib.tsa_align_batch_ends.argtypes = [u8p, i64p, ctypes.c_int32, pp, ctypes.c_int32, i32p, u8p, i32p, i32p, i32p,
                                          ctypes.c_int32]
+    lib.tsa_align_batch_grid_ends.argtypes = lib.tsa_align_batch_ends.argtypes
     lib.tsa_score_batch_ends.argtypes = [u8p, i64p, ctypes.c_int32, pp, ctypes.c_int32, i32p, i32p, ctypes.c_int32]
     lib.tsa_score_ends_workspace_size.argtypes = [ctypes.c_int32] * 4 + [pp, ctypes.c_int32,
                                                                         ctypes.POINTER(ctypes.c_size_t)]
@@ -205,7 +206,8 @@ def _load_lib() -> ctypes.CDLL:
                  "tsa_get_overrides", "tsa_align_batch", "tsa_describe_align_plan",
                  "tsa_align_batch_lowmem", "tsa_align_batch_grid", "tsa_align_workspace_size",
                  "tsa_align_batch_async", "tsa_align_rows_async", "tsa_align_batch_ends", "tsa_score_batch_ends",
-                 "tsa_score_ends_workspace_size", "tsa_score_batch_ends_async", "tsa_describe_score_ends_plan"):
+                 "tsa_score_ends_workspace_size", "tsa_score_batch_ends_async", "tsa_describe_score_ends_plan",
+                 "tsa_align_batch_grid_ends"):
         getattr(lib, name).restype = ctypes.c_int
     return lib
 
@@ -449,7 +451,8 @@ def align_batch(triples=None, params: Optional[TsaParams] = None, device: int = 
 
 
 def align_batch_ends(triples=None, params: Optional[TsaParams] = None, end: str | int = "any", device: int = 0,
-                     seqs: Optional[np.ndarray] = None, offsets: Optional[np.ndarray] = None) -> list:
+                     seqs: Optional[np.ndarray] = None, offsets: Optional[np.ndarray] = None,
+                     grid: bool = False) -> list:
     """``align_batch`` with a free end (tsa_align_batch_ends): a list of
     ``(score, start, moves, end)``, one per triple in the caller's order.
 
@@ -465,7 +468,16 @@ def align_batch_ends(triples=None, params: Optional[TsaParams] = None, end: str 
     ``render_alignment`` work from ``start`` and ``moves`` alone, so they take
     these results as they are. Under "face" and "any" the larger triples
     always take the tiled resident kernel, and ``align_mode`` set to plane,
-    strip or grid raises ``TsaError(TSA_EINVAL)``."""
+    strip or grid raises ``TsaError(TSA_EINVAL)``.
+
+    ``grid=True`` calls tsa_align_batch_grid_ends: the same results, move for
+    move, with the larger triples on the grid path (``align_mode="grid"``
+    unless that override is set), so a triple needs its tile cube and its kept
+    faces instead of its whole pointer cube, as under ``align_batch(grid=True)``.
+    The forward launches then search the end as they sweep every tile, and the
+    backward launches start at the end cell's tile. ``align_mode`` set to
+    resident or tiled holds; plane or strip raises ``TsaError(TSA_EINVAL)``
+    under "face" and "any"; "corner" is ``align_batch(grid=True)``'s path."""
     mode = END_MODES.get(end, end) if isinstance(end, str) else end
     if isinstance(mode, (str, bool)) or not isinstance(mode, (int, np.integer)):
         raise TsaError(TSA_EINVAL, f"align_batch_ends(end={end!r})")
@@ -480,10 +492,11 @@ def align_batch_ends(triples=None, params: Optional[TsaParams] = None, end: str 
     st = np.zeros(max(3 * n, 1), dtype=np.int32)
     en = np.zeros(max(3 * n, 1), dtype=np.int32)
     mv = np.zeros(max(int(offsets[-1] - offsets[0]) if n else 0, 1), dtype=np.uint8)
-    rc = _lib.tsa_align_batch_ends(_ptr(seqs, ctypes.c_uint8), _ptr(offsets, ctypes.c_int64), n, ctypes.byref(p),
-                                   int(mode), _ptr(sc, ctypes.c_int32), _ptr(mv, ctypes.c_uint8),
-                                   _ptr(nm, ctypes.c_int32), _ptr(st, ctypes.c_int32), _ptr(en, ctypes.c_int32), device)
-    _check(rc, "tsa_align_batch_ends")
+    name = "tsa_align_batch_grid_ends" if grid else "tsa_align_batch_ends"
+    rc = getattr(_lib, name)(_ptr(seqs, ctypes.c_uint8), _ptr(offsets, ctypes.c_int64), n, ctypes.byref(p),
+                             int(mode), _ptr(sc, ctypes.c_int32), _ptr(mv, ctypes.c_uint8),
+                             _ptr(nm, ctypes.c_int32), _ptr(st, ctypes.c_int32), _ptr(en, ctypes.c_int32), device)
+    _check(rc, name)
     at = (offsets[0:3 * n:3] - offsets[0]).tolist()
     return [(s, tuple(s0), mv[m0:m0 + k].copy(), tuple(e))
             for s, s0, m0, k, e in zip(sc[:n].tolist(), st[:3 * n].reshape(-1, 3).tolist(), at, nm[:n].tolist(),

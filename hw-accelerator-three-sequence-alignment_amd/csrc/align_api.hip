@@ -1,7 +1,8 @@
 // align_api.hip -- the traceback entry points of include/trialign.h:
 // tsa_align_batch, tsa_align_batch_lowmem, tsa_align_batch_grid, tsa_align_batch_ends
 // (tsa_align_batch with a free end: the resident and the tiled kernel search
-// the end cell as they sweep, tb_walk_ends walks from it), tsa_align_gpu
+// the end cell as they sweep, tb_walk_ends walks from it), tsa_align_batch_grid_ends
+// (the same search by the grid kernels, a key per tile), tsa_align_gpu
 // (one triple, always the plane sweep), tsa_describe_align_plan and the
 // device-resident tsa_align_workspace_size, tsa_align_batch_async and
 // tsa_align_rows_async, which plan with the same planner against a caller's
@@ -100,7 +101,8 @@ int align_plan_read(AlignPlan *pl) {
 
 // The path of the over-capacity triples of a group that holds n_over of them.
 AlignPath align_over_path(const AlignPlan &pl, int32_t n_over) {
-  if (pl.end_mode != TSA_END_CORNER) return ALIGN_TILED;  // tsa_align_batch_ends: whatever their number
+  // tsa_align_batch_ends: tiled, whatever their number; tsa_align_batch_grid_ends: grid
+  if (pl.end_mode != TSA_END_CORNER) return pl.mode == ALIGN_MODE_GRID ? ALIGN_GRID : ALIGN_TILED;
   if (pl.mode == ALIGN_MODE_TILED) return ALIGN_TILED;
   if (pl.mode == ALIGN_MODE_STRIP) return ALIGN_STRIP;
   if (pl.mode == ALIGN_MODE_GRID) return ALIGN_GRID;
@@ -134,6 +136,7 @@ struct AlignChunk {
   bool tiled = false, strip = false, grid = false;  // the path of the n_over over-capacity triples
   int32_t max_nty = 0;                    // the strip launches: the most strips of a triple
   int32_t max_diag = 0, max_len = 0;      // the grid launches: the most diagonals (nty+ntz-1), the longest diagonal
+  size_t slots = 0;                       // the end keys of its grid triples, one per tile (tsa_align_batch_grid_ends)
   size_t need = 0, cube = 0, seq = 0;     // bytes against the budget, of the cubes and of the sequences
   int64_t max_pos = 1, tile_pos = 1;      // the resident and the tiled launch
   size_t lds = 0, tile_lds = 0, face = 0; // face: bytes
@@ -188,6 +191,7 @@ int align_plan_chunks(const std::vector<AlignTriple> &T, const AlignPlan &pl, si
       c.face += sizeof(uint4) * t.face;
       c.max_nty = std::max(c.max_nty, t.nty);
       c.max_diag = std::max(c.max_diag, t.nty + t.ntz - 1), c.max_len = std::max(c.max_len, std::min(t.nty, t.ntz));
+      c.slots += (size_t)t.nty * t.ntz;
       c.mla = std::max(c.mla, t.la), c.mlb = std::max(c.mlb, t.lb), c.mlc = std::max(c.mlc, t.lc);
     }
     c.i0 = i, c.i1 = j;
@@ -220,6 +224,11 @@ struct AlignDev {
   // TSA_END_ANY), ALIGN_END_REC words a triple; they lie on final7, which the
   // kernels of those modes do not write.
   int32_t *endrec;
+  // The end keys of the chunk's grid triples under tsa_align_batch_grid_ends,
+  // one slot per tile, and the key offset of every triple's slots (entry mr on
+  // is the first grid triple's, as tboff's).
+  uint64_t *slots;
+  const int64_t *slotoff;
 };
 
 // Queues the sweeps and walks of chunk c on stream s.
@@ -263,18 +272,28 @@ int align_queue_chunk(const AlignChunk &c, const AlignPlan &pl, const KParams &k
   if (c.grid) {
     // forward: diagonal by diagonal, every tile but the last of each triple;
     // then the tile each walker stands in, followed by the walk of its pointers,
-    // as often as the longest path can change tiles
-    for (int32_t j = 0; j < 2 * c.max_diag - 1; ++j) {
-      const bool fwd = j < c.max_diag - 1;
-      const int32_t dg = fwd ? j : j - (c.max_diag - 1);
+    // as often as the longest path can change tiles. With a free end the
+    // forward form sweeps the last tile as well, one diagonal more, and the end
+    // records follow it: the walks then start from their records (j + 1), and
+    // the host, which does not know the end tiles, still queues the worst case
+    // of backward launches.
+    const bool ends = pl.end_mode != TSA_END_CORNER;
+    const int32_t nfwd = ends ? c.max_diag : c.max_diag - 1;
+    for (int32_t j = 0; j < nfwd + c.max_diag; ++j) {
+      const bool fwd = j < nfwd;
+      const int32_t dg = fwd ? j : j - nfwd;
       if ((rc = align_launch_grid(d.seqs, d.off + 3 * (size_t)mr, c.n_over, pl.tymax, pl.tzmax, c.tile_pos,
                                   c.tile_lds, kp, fwd, dg, c.max_len, d.walk, d.scores + mr,
-                                  d.final7 + (size_t)NSTATE * mr, d.tb, d.tboff + mr, d.faces, d.faceoff + mr, s)))
+                                  d.final7 + (size_t)NSTATE * mr, d.tb, d.tboff + mr, d.faces, d.faceoff + mr, s,
+                                  pl.end_mode, d.slots, ends ? d.slotoff + mr : nullptr)))
         return rc;
+      if (ends && j == nfwd - 1)
+        align_launch_grid_end(d.off + 3 * (size_t)mr, c.n_over, pl.tymax, pl.tzmax, d.slots, d.slotoff + mr,
+                              d.scores + mr, d.endrec + (size_t)ALIGN_END_REC * mr, d.walk, d.info + 4 * (size_t)mr, s);
       if (!fwd)
         hipLaunchKernelGGL(tb_walk_grid, dim3((c.n_over + 63) / 64), dim3(64), 0, s, d.tb, d.tboff + mr,
-                           d.off + 3 * (size_t)mr, c.n_over, pl.tymax, pl.tzmax, dg, d.final7 + (size_t)NSTATE * mr,
-                           d.walk, d.moves, d.info + 4 * (size_t)mr);
+                           d.off + 3 * (size_t)mr, c.n_over, pl.tymax, pl.tzmax, ends ? dg + 1 : dg,
+                           d.final7 + (size_t)NSTATE * mr, d.walk, d.moves, d.info + 4 * (size_t)mr);
     }
   }
   return TSA_OK;
@@ -289,24 +308,28 @@ int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KPar
   std::vector<AlignChunk> chunks;
   int rc = align_plan_chunks(T, pl, budget, &chunks);
   if (rc) return rc;
-  size_t max_cube = 0, max_seq = 0, max_ws = 0, max_face = 0;
+  // the end keys of a chunk's grid triples: beside the walker records, outside the budget like them
+  const bool keyed = pl.end_mode != TSA_END_CORNER && pl.mode == ALIGN_MODE_GRID;
+  size_t max_cube = 0, max_seq = 0, max_ws = 0, max_face = 0, max_slots = 0;
   int32_t max_n = 0;
   for (const AlignChunk &c : chunks) {
     max_cube = std::max(max_cube, c.cube), max_seq = std::max(max_seq, c.seq);
     max_ws = std::max(max_ws, c.ws), max_face = std::max(max_face, c.face);
+    if (keyed && c.grid) max_slots = std::max(max_slots, c.slots);
     max_n = std::max(max_n, c.i1 - c.i0);
   }
   // device buffers, once per call, sized for the largest chunk
   AlignBufs B;
   uint8_t *d_seqs = nullptr, *d_moves = nullptr;
-  int64_t *d_meta = nullptr;  // [0, 3m] offsets, then m cube word offsets, then m face cell offsets
+  int64_t *d_meta = nullptr;  // [0, 3m] offsets, then m cube word offsets, m face cell offsets, m slot offsets
   int32_t *d_res = nullptr;   // m scores, 7m final states, 4m walk infos
   uint32_t *d_tb = nullptr;
   void *d_ws = nullptr, *d_faces = nullptr;
   int32_t *d_walk = nullptr;  // the walker records of a chunk's strip or grid triples
+  uint64_t *d_slots = nullptr;
   if (hipStreamCreateWithFlags(&B.s, hipStreamNonBlocking) != hipSuccess) return TSA_EDEVICE;
   if (!B.alloc(&d_seqs, max_seq) || !B.alloc(&d_moves, max_seq) ||
-      !B.alloc(&d_meta, sizeof(int64_t) * (5 * (size_t)max_n + 1)) ||
+      !B.alloc(&d_meta, sizeof(int64_t) * (6 * (size_t)max_n + 1)) || !B.alloc(&d_slots, sizeof(uint64_t) * max_slots) ||
       !B.alloc(&d_res, sizeof(int32_t) * 12 * (size_t)max_n) || !B.alloc(&d_tb, max_cube) ||
       !B.alloc(&d_ws, max_ws) || !B.alloc(&d_faces, max_face) ||
       !B.alloc(&d_walk, pl.mode == ALIGN_MODE_STRIP || pl.mode == ALIGN_MODE_GRID
@@ -314,15 +337,16 @@ int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KPar
                             : 0))
     return TSA_ENOMEM;
   std::vector<uint8_t> h_seqs(max_seq), h_moves(max_seq);
-  std::vector<int64_t> h_meta(5 * (size_t)max_n + 1);
+  std::vector<int64_t> h_meta(6 * (size_t)max_n + 1);
   std::vector<int32_t> h_res(12 * (size_t)max_n), order((size_t)max_n);
   for (const AlignChunk &c : chunks) {
     // launch order: resident triples first, then the over-capacity ones
     const int32_t m = c.i1 - c.i0, mr = m - c.n_over;
     int32_t r = 0, v = mr;
     for (int32_t i = c.i0; i < c.i1; ++i) order[T[i].over ? v++ : r++] = i;
-    int64_t pos = 0, word = 0, cells = 0;
+    int64_t pos = 0, word = 0, cells = 0, keys = 0;
     int64_t *h_off = h_meta.data(), *h_tboff = h_meta.data() + 3 * (size_t)m + 1, *h_faceoff = h_tboff + m;
+    int64_t *h_slotoff = h_faceoff + m;
     for (int32_t j = 0; j < m; ++j) {
       const AlignTriple &t = T[order[j]];
       std::memcpy(h_seqs.data() + pos, seqs + offsets[3 * (int64_t)order[j]], (size_t)t.la + t.lb + t.lc);
@@ -332,6 +356,8 @@ int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KPar
       word += (int64_t)(t.cube / sizeof(uint32_t));
       h_faceoff[j] = cells;
       if (c.tiled || c.strip || c.grid) cells += (int64_t)t.face;
+      h_slotoff[j] = keys;
+      if (keyed && c.grid && t.over) keys += (int64_t)t.nty * t.ntz;
     }
     h_off[3 * m] = pos;
     AlignDev d;
@@ -339,8 +365,9 @@ int align_run(const uint8_t *seqs, const int64_t *offsets, int32_t n, const KPar
     d.scores = d_res, d.final7 = d_res + m, d.info = d_res + 8 * (size_t)m;
     d.moves = d_moves, d.tb = d_tb, d.faces = d_faces, d.ws = d_ws, d.walk = d_walk;
     d.endrec = d.final7;
+    d.slots = d_slots, d.slotoff = d.faceoff + m;
     if (hipMemcpyAsync(d_seqs, h_seqs.data(), (size_t)pos, hipMemcpyHostToDevice, B.s) != hipSuccess ||
-        hipMemcpyAsync(d_meta, h_meta.data(), sizeof(int64_t) * (5 * (size_t)m + 1), hipMemcpyHostToDevice, B.s) !=
+        hipMemcpyAsync(d_meta, h_meta.data(), sizeof(int64_t) * (6 * (size_t)m + 1), hipMemcpyHostToDevice, B.s) !=
             hipSuccess)
       return TSA_EDEVICE;
     if ((rc = align_queue_chunk(c, pl, kp, d, B.s))) return rc;
@@ -497,10 +524,13 @@ int align_batch_entry(const uint8_t *seqs, const int64_t *offsets, int32_t n, co
   AlignPlan pl;
   int rc = TSA_OK;
   if (end_mode != TSA_END_CORNER) {
-    // the end search is the resident and the tiled kernel's: no plane sweep, no
-    // strips, no grid -- a matter of the arguments, so it is found without a device
+    // the end search is the resident and the tiled kernel's, and the grid
+    // kernels' under tsa_align_batch_grid_ends (unset = grid) alone: no plane
+    // sweep, no strips -- a matter of the arguments, so it is found without a device
     if ((rc = align_plan_read(&pl))) return rc;
-    if (pl.mode == ALIGN_MODE_PLANE || pl.mode == ALIGN_MODE_STRIP || pl.mode == ALIGN_MODE_GRID) return TSA_EINVAL;
+    if (pl.mode == ALIGN_MODE_PLANE || pl.mode == ALIGN_MODE_STRIP ||
+        (pl.mode == ALIGN_MODE_GRID && unset != ALIGN_MODE_GRID))
+      return TSA_EINVAL;
   }
   const int nd = tsa_device_count();
   if (nd <= 0) return TSA_ENODEV;
@@ -560,6 +590,13 @@ int tsa_align_batch_ends(const uint8_t *seqs, const int64_t *offsets, int32_t n,
   return align_batch_entry(seqs, offsets, n, p, scores, moves, n_moves, starts, device, ALIGN_MODE_AUTO, end_mode, ends);
 }
 
+int tsa_align_batch_grid_ends(const uint8_t *seqs, const int64_t *offsets, int32_t n, const tsa_params *p,
+                              int32_t end_mode, int32_t *scores, uint8_t *moves, int32_t *n_moves, int32_t *starts,
+                              int32_t *ends, int32_t device) {
+  if (!ends || end_mode < TSA_END_CORNER || end_mode > TSA_END_ANY) return TSA_EINVAL;
+  return align_batch_entry(seqs, offsets, n, p, scores, moves, n_moves, starts, device, ALIGN_MODE_GRID, end_mode, ends);
+}
+
 int tsa_align_workspace_size(const int64_t *h_offsets, int32_t n, const tsa_params *p, int32_t path,
                              size_t *min_bytes, size_t *full_bytes) {
   if (!min_bytes || !full_bytes) return TSA_EINVAL;
@@ -613,7 +650,7 @@ int tsa_align_batch_async(const uint8_t *d_seqs, const int64_t *d_offsets, const
     // the faces (16-byte cells) first, then the cubes (words): c.face + c.cube = c.need bytes
     d.faces = w + f.total, d.tb = (uint32_t *)(w + f.total + c.face), d.ws = nullptr;
     d.walk = (int32_t *)(w + f.walk) + (size_t)ALIGN_WALK_REC * c.i0;
-    d.endrec = nullptr;  // no end-free form on this path
+    d.endrec = nullptr, d.slots = nullptr, d.slotoff = nullptr;  // no end-free form on this path
     align_launch_meta(d_offsets, c.i0, m, A.pl, b, s);
     align_launch_pack(d_seqs, d_offsets, m, b, s);
     if ((rc = align_queue_chunk(c, A.pl, kp, d, s))) return rc;

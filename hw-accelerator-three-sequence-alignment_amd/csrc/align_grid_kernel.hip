@@ -43,6 +43,31 @@
 // cell, the face threads copy one step late. No workgroup waits for another:
 // there is no flag, fence or poll. Launches of one stream order the diagonals,
 // a tile's sweep, its walk and the next sweep, which overwrites the tile cube.
+//
+// The END forms (tsa_align_batch_grid_ends under TSA_END_FACE / TSA_END_ANY)
+// search the cell the path ends in as the resident kernels do, by align_step.h's
+// 64-bit key:
+//
+//   forward END    launch d = 0 .. nty+ntz-2 sweeps every tile, the last one
+//                  included (it stores no face), and every cell that may end
+//                  the path folds its key into the thread's running best. After
+//                  its last step the workgroup reduces its keys and thread 0
+//                  stores the tile's key into the slot ty*ntz+tz of the triple's
+//                  nty*ntz slots. Every tile writes its slot in every call, so
+//                  the slots are never cleared, and a plain max has no order, so
+//                  no atomics either.
+//   end record     align_grid_end_kernel, one thread per triple, takes the max
+//                  over the slots and writes the score, the end record
+//                  {x1, y1, z1, state, score} and the walker record
+//                  {x1, y1, z1, state, 0, 0}.
+//   backward END   launch 0 reads the walker record like every later launch:
+//                  the tile of (y1,z1), x <= x1. Its step stores pointer words
+//                  alone (ALIGN_END_PTRS): when the end lies in the last tile
+//                  with x1 = la the swept cells hold (la,lb,lc), and the corner's
+//                  score and final states would overwrite the end's score and
+//                  the end record, which lies on final7. tb_walk_grid is
+//                  launched with j + 1, so it takes cell and state from the
+//                  record from the first segment on.
 
 #include "align_kernel.h"
 #include "align_step.h"
@@ -55,7 +80,10 @@ constexpr int GRID_NT = 1024;  // as the tiled kernel's: align_tile_fits bounds 
 // FWD: launch d of the forward form (walk is not read). Otherwise launch d of
 // the backward form; walk = the walker records of tb_walk_grid, ALIGN_WALK_REC
 // words a triple.
-template <int K, bool FWD>
+// END = TSA_END_FACE / TSA_END_ANY: the forward END form, where tb and tb_off
+// are not the cubes' but the key slots' -- (uint64_t *)tb + tb_off[t] = the
+// nty*ntz slots of triple t -- or, for any END != 0, the backward END form.
+template <int K, bool FWD, int END = TSA_END_CORNER>
 __global__ __launch_bounds__(GRID_NT) void align_grid_kernel(
     const uint8_t *__restrict__ seqs, const int64_t *__restrict__ offs, KParams kp, uint32_t lds_bytes,
     int32_t tymax, int32_t tzmax, int32_t d, const int32_t *__restrict__ walk, int32_t *__restrict__ scores,
@@ -73,8 +101,9 @@ __global__ __launch_bounds__(GRID_NT) void align_grid_kernel(
   if (FWD) {
     ty = max(0, d - (tg.ntz - 1)) + (int32_t)blockIdx.y;
     tz = d - ty;
-    if (ty >= tg.nty || tz < 0 || (ty == tg.nty - 1 && tz == tg.ntz - 1)) return;
-  } else if (d == 0) {
+    if (ty >= tg.nty || tz < 0 || (END == TSA_END_CORNER && ty == tg.nty - 1 && tz == tg.ntz - 1))
+      return;
+  } else if (END == TSA_END_CORNER && d == 0) {
     ty = tg.nty - 1, tz = tg.ntz - 1;
   } else {
     const int32_t *rec = walk + ALIGN_WALK_REC * t;
@@ -109,6 +138,7 @@ __global__ __launch_bounds__(GRID_NT) void align_grid_kernel(
   uint32_t meta[K], gh[K];
   int32_t hXY[K], hYZ[K], hXZ[K], hM3[K], hM2[K];
   auto P = [&](int k) { return AlignPos{meta[k], gh[k], hXY[k], hYZ[k], hXZ[k], hM3[k], hM2[k]}; };
+  [[maybe_unused]] AlignEnd end;  // the running best of the thread (forward END form)
 #pragma unroll
   for (int k = 0; k < K; ++k) P(k).init(k * nt + tid, tyl, tzl, sB, sC);
   const int32_t qmax = xm + tyl + tzl + ((ywr || zwr) ? 1 : 0);
@@ -116,8 +146,16 @@ __global__ __launch_bounds__(GRID_NT) void align_grid_kernel(
     const uint4 *rd = (q & 1) ? buf0 : buf1;  // buf[(q-1)&1]
     uint4 *wr = (q & 1) ? buf1 : buf0;        // buf[q&1]
 #pragma unroll
-    for (int k = 0; k < K; ++k)
-      P(k).template step<!FWD>(rd, wr, ldz, q, xm, y0, z0, lb, lc, cube, kp, t, scores, final7, symA, TZ);
+    for (int k = 0; k < K; ++k) {
+      if constexpr (END == TSA_END_CORNER)
+        P(k).template step<!FWD>(rd, wr, ldz, q, xm, y0, z0, lb, lc, cube, kp, t, scores, final7, symA, TZ);
+      else if constexpr (FWD)
+        P(k).template step<false, END>(rd, wr, ldz, q, xm, y0, z0, lb, lc, cube, kp, t, scores, final7, symA, TZ,
+                                       &end);
+      else
+        P(k).template step<true, ALIGN_END_PTRS>(rd, wr, ldz, q, xm, y0, z0, lb, lc, cube, kp, t, scores, final7,
+                                                 symA, TZ);
+    }
     // the face threads, as the tiled kernel's: f = 0 the corner, 1 .. tzl
     // row 0 and the last local row, tzl+1 .. tzl+tyl column 0 and the last
     // local column
@@ -136,6 +174,47 @@ __global__ __launch_bounds__(GRID_NT) void align_grid_kernel(
     }
     __syncthreads();
   }
+  if constexpr (FWD && END != TSA_END_CORNER) {
+    const uint64_t key = align_end_reduce_key(end, (uint64_t *)smem, tid, nt);
+    if (tid == 0) ((uint64_t *)tb)[tb_off[t] + (int64_t)ty * tg.ntz + tz] = key;
+  }
+}
+
+// The end record of every grid triple from the keys of its tiles, one thread
+// per triple: the largest key decoded into endrec[5t ..] and scores[t], and the
+// walker record {x1, y1, z1, state, 0, 0} the backward END form starts from. A
+// key that names no cell of the cube (0: no slot written) ends the triple at
+// once with info[4t] = 0 moves, which the host reports as TSA_EINTERNAL.
+__global__ __launch_bounds__(64) void align_grid_end_kernel(const int64_t *__restrict__ offs, int32_t n, int32_t tymax,
+                                                            int32_t tzmax, const uint64_t *__restrict__ slots,
+                                                            const int64_t *__restrict__ slot_off,
+                                                            int32_t *__restrict__ scores, int32_t *__restrict__ endrec,
+                                                            int32_t *__restrict__ walk, int32_t *__restrict__ info) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const int64_t o0 = offs[3 * t], o1 = offs[3 * t + 1], o2 = offs[3 * t + 2], o3 = offs[3 * t + 3];
+  const int32_t la = (int32_t)(o1 - o0), lb = (int32_t)(o2 - o1), lc = (int32_t)(o3 - o2);
+  const AlignTileGeom tg = align_tile_geom(lb, lc, tymax, tzmax);
+  const uint64_t *s = slots + slot_off[t];
+  uint64_t k = 0;
+  for (int32_t i = 0; i < tg.nty * tg.ntz; ++i) k = max(k, s[i]);
+  int32_t e[ALIGN_END_REC];
+  align_end_decode(k, lb, lc, e);
+  const bool ok = k && e[0] >= 1 && e[0] <= la && e[1] >= 1 && e[1] <= lb && e[2] >= 1 && e[2] <= lc && e[3] >= 0 &&
+                  e[3] < NSTATE;
+  for (int i = 0; i < ALIGN_END_REC; ++i) endrec[ALIGN_END_REC * t + i] = e[i];
+  scores[t] = e[4];
+  int32_t *rec = walk + ALIGN_WALK_REC * t;
+  rec[0] = e[0], rec[1] = e[1], rec[2] = e[2], rec[3] = e[3], rec[4] = 0, rec[5] = ok ? 0 : 1;
+  if (!ok) info[4 * t] = 0;
+}
+
+void align_launch_grid_end(const int64_t *d_offsets, int32_t n, int32_t tymax, int32_t tzmax, const uint64_t *d_slots,
+                           const int64_t *d_slot_off, int32_t *d_scores, int32_t *d_endrec, int32_t *d_walk,
+                           int32_t *d_info, hipStream_t stream) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(align_grid_end_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, d_offsets, n, tymax, tzmax,
+                     d_slots, d_slot_off, d_scores, d_endrec, d_walk, d_info);
 }
 
 // One launch for n triples: fwd the forward form's launch d over a grid of
@@ -143,16 +222,25 @@ __global__ __launch_bounds__(GRID_NT) void align_grid_kernel(
 // backward form, triple = workgroup. The tile caps, max_pos and lds as
 // align_launch_tiled's; d_tb_off[t] = the word offset of triple t's tile cube,
 // d_face_off[t] = the cell offset of its align_grid_face_cells in d_faces.
+// end_mode = TSA_END_FACE / TSA_END_ANY: the END forms, with d_slots and
+// d_slot_off[t] = the key offset of triple t's nty*ntz slots.
 int align_launch_grid(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, int32_t tymax, int32_t tzmax,
                       int64_t max_pos, size_t lds, const KParams &kp, bool fwd, int32_t d, int32_t ndiag,
                       const int32_t *d_walk, int32_t *d_scores, int32_t *d_final7, uint32_t *d_tb,
-                      const int64_t *d_tb_off, void *d_faces, const int64_t *d_face_off, hipStream_t stream) {
+                      const int64_t *d_tb_off, void *d_faces, const int64_t *d_face_off, hipStream_t stream,
+                      int32_t end_mode, uint64_t *d_slots, const int64_t *d_slot_off) {
   if (n <= 0) return TSA_OK;
+  if (end_mode < TSA_END_CORNER || end_mode > TSA_END_ANY || (end_mode != TSA_END_CORNER && (!d_slots || !d_slot_off)))
+    return TSA_EINVAL;
   if (!align_tile_fits(tymax, tzmax) || max_pos < 1 || max_pos > (int64_t)tymax * tzmax || lds > LDS_MAX || !d_tb ||
       !d_tb_off || !d_faces || !d_face_off || !d_walk || d < 0 || (fwd && (ndiag < 1 || ndiag > 65535)))
     return TSA_EINVAL;
   const int k = (int)((max_pos + GRID_NT - 1) / GRID_NT);
   const int nt = (int)(((max_pos + k - 1) / k + 63) / 64 * 64);
+  if (fwd && end_mode != TSA_END_CORNER) {  // the forward END form takes the slots where the others take the cubes
+    d_tb = (uint32_t *)d_slots;
+    d_tb_off = d_slot_off;
+  }
   auto launch = [&](auto kfn) {
     return launch_with_lds((const void *)kfn, lds, [&] {
              hipLaunchKernelGGL(kfn, dim3(n, fwd ? ndiag : 1), dim3(nt), lds, stream, d_seqs, d_offsets, kp,
@@ -162,6 +250,21 @@ int align_launch_grid(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n
                ? TSA_OK
                : TSA_EDEVICE;
   };
+  if (fwd && end_mode == TSA_END_FACE) {
+    if (k == 1) return launch(align_grid_kernel<1, true, TSA_END_FACE>);
+    if (k == 2) return launch(align_grid_kernel<2, true, TSA_END_FACE>);
+    return launch(align_grid_kernel<3, true, TSA_END_FACE>);
+  }
+  if (fwd && end_mode == TSA_END_ANY) {
+    if (k == 1) return launch(align_grid_kernel<1, true, TSA_END_ANY>);
+    if (k == 2) return launch(align_grid_kernel<2, true, TSA_END_ANY>);
+    return launch(align_grid_kernel<3, true, TSA_END_ANY>);
+  }
+  if (end_mode != TSA_END_CORNER) {  // backward: one form for both modes
+    if (k == 1) return launch(align_grid_kernel<1, false, ALIGN_END_PTRS>);
+    if (k == 2) return launch(align_grid_kernel<2, false, ALIGN_END_PTRS>);
+    return launch(align_grid_kernel<3, false, ALIGN_END_PTRS>);
+  }
   if (fwd) {
     if (k == 1) return launch(align_grid_kernel<1, true>);
     if (k == 2) return launch(align_grid_kernel<2, true>);

@@ -73,6 +73,9 @@ int align_launch_resident(const uint8_t *d_seqs, const int64_t *d_offsets, int32
 // cell's MAX7. The kernels find it through a 64-bit key per cell (align_step.h)
 // whose position field holds the cell's number in (x,y,z) order, below la*lb*lc.
 constexpr int ALIGN_END_REC = 5;
+// AlignPos::step's END of a sweep that follows the search (the backward END
+// form of the grid kernels): neither an end key nor the corner's score.
+constexpr int ALIGN_END_PTRS = -1;
 constexpr int ALIGN_END_POS_BITS = 45;
 constexpr uint64_t ALIGN_END_POS_MASK = (1ull << ALIGN_END_POS_BITS) - 1;
 // Every cube whose pointers fit device memory passes: it has more than
@@ -195,10 +198,26 @@ __host__ __device__ inline size_t align_grid_face_cells(int32_t la, int32_t lb, 
 // record: the tile of (lb,lc), all of x). max_pos, lds and d_face_off as
 // align_launch_tiled's, over align_grid_face_cells; d_tb_off[t] = the word
 // offset of triple t's tile cube.
+// end_mode = TSA_END_FACE / TSA_END_ANY (tsa_align_batch_grid_ends): the END
+// forms. Forward launch d = 0 .. nty+ntz-2 sweeps the last tile too, and every
+// tile stores the largest end key of its cells into its own slot,
+// d_slots[d_slot_off[t] + ty*ntz + tz]; align_launch_grid_end then makes the
+// records; backward launch d = 0 reads the triple's record like every later
+// one and no backward launch writes d_scores or d_final7.
 int align_launch_grid(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, int32_t tymax, int32_t tzmax,
                       int64_t max_pos, size_t lds, const KParams &kp, bool fwd, int32_t d, int32_t ndiag,
                       const int32_t *d_walk, int32_t *d_scores, int32_t *d_final7, uint32_t *d_tb,
-                      const int64_t *d_tb_off, void *d_faces, const int64_t *d_face_off, hipStream_t stream);
+                      const int64_t *d_tb_off, void *d_faces, const int64_t *d_face_off, hipStream_t stream,
+                      int32_t end_mode = TSA_END_CORNER, uint64_t *d_slots = nullptr,
+                      const int64_t *d_slot_off = nullptr);
+// After the last forward END launch, one thread per triple (not a counted
+// launch): the max over the triple's nty*ntz slots, decoded into d_scores[t],
+// the end record d_endrec[5t ..] and the walker record d_walk[6t ..] =
+// {x1, y1, z1, state, 0, 0}. A key that names no cell of the cube marks the
+// record done and sets d_info[4t] = 0 moves (TSA_EINTERNAL on the host).
+void align_launch_grid_end(const int64_t *d_offsets, int32_t n, int32_t tymax, int32_t tzmax, const uint64_t *d_slots,
+                           const int64_t *d_slot_off, int32_t *d_scores, int32_t *d_endrec, int32_t *d_walk,
+                           int32_t *d_info, hipStream_t stream);
 // The walk after backward launch j, one walker (thread) per triple: it follows
 // the pointers of the tile its record stands in (from (la,lb,lc) and final7
 // when j = 0) while the cell lies in that tile, appending to moves[offs[3t] ..)
@@ -223,7 +242,7 @@ struct AlignPlan {
   int32_t mode_set = 0;  // align_mode is set
   int32_t capped = 0;    // align_tile is set
   int32_t tymax = ALIGN_TILE_Y, tzmax = ALIGN_TILE_Z;
-  int32_t end_mode = 0;  // TSA_END_FACE / TSA_END_ANY: every over-capacity triple is tiled
+  int32_t end_mode = 0;  // TSA_END_FACE / TSA_END_ANY: every over-capacity triple is tiled, or grid under mode = grid
 };
 // Over capacity: the triple does not go to the resident kernel as a whole.
 // With align_tile set under align_mode = tiled, strip or grid that is any triple

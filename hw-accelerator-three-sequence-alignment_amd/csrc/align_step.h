@@ -74,12 +74,22 @@ struct AlignEnd {
   }
 };
 
+// A key back into the end record rec = {x1, y1, z1, state, score} of a cube
+// whose rows are lc long and whose planes have lb rows.
+__device__ __forceinline__ void align_end_decode(uint64_t k, int32_t lb, int32_t lc, int32_t *rec) {
+  const uint64_t pos = ~(k >> 3) & ALIGN_END_POS_MASK, row = pos / (uint32_t)lc;
+  rec[0] = (int32_t)(row / (uint32_t)lb) + 1;
+  rec[1] = (int32_t)(row % (uint32_t)lb) + 1;
+  rec[2] = (int32_t)(pos % (uint32_t)lc) + 1;
+  rec[3] = 7 - (int32_t)(k & 7u);
+  rec[4] = (int32_t)(k >> 48) - 32768;
+}
+
 // The workgroup's best key after its last step (whose barrier lies behind, so
 // slots, LDS for one key per wave, may be the cell buffers): a wave reduce,
-// then thread 0 over the waves' keys, which writes the triple's end record
-// rec = {x1, y1, z1, state, score} and its score.
-__device__ __forceinline__ void align_end_reduce(const AlignEnd &end, uint64_t *slots, int tid, int nt, int32_t lb,
-                                                 int32_t lc, int32_t *rec, int32_t *score) {
+// then thread 0 over the waves' keys. The return value is the workgroup's key
+// in thread 0 alone.
+__device__ __forceinline__ uint64_t align_end_reduce_key(const AlignEnd &end, uint64_t *slots, int tid, int nt) {
   uint64_t k = end.best;
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) {
@@ -88,16 +98,19 @@ __device__ __forceinline__ void align_end_reduce(const AlignEnd &end, uint64_t *
   }
   if ((tid & 63) == 0) slots[tid >> 6] = k;
   __syncthreads();
-  if (tid == 0) {
+  if (tid == 0)
     for (int w = 1; w < nt / 64; ++w) k = max(k, slots[w]);
-    const uint64_t pos = ~(k >> 3) & ALIGN_END_POS_MASK, row = pos / (uint32_t)lc;
-    const int32_t sc = (int32_t)(k >> 48) - 32768;
-    rec[0] = (int32_t)(row / (uint32_t)lb) + 1;
-    rec[1] = (int32_t)(row % (uint32_t)lb) + 1;
-    rec[2] = (int32_t)(pos % (uint32_t)lc) + 1;
-    rec[3] = 7 - (int32_t)(k & 7u);
-    rec[4] = sc;
-    *score = sc;
+  return k;
+}
+
+// A workgroup that has swept the whole cube: thread 0 writes the triple's end
+// record and its score.
+__device__ __forceinline__ void align_end_reduce(const AlignEnd &end, uint64_t *slots, int tid, int nt, int32_t lb,
+                                                 int32_t lc, int32_t *rec, int32_t *score) {
+  const uint64_t k = align_end_reduce_key(end, slots, tid, nt);
+  if (tid == 0) {
+    align_end_decode(k, lb, lc, rec);
+    *score = rec[4];
   }
 }
 
@@ -138,7 +151,11 @@ struct AlignPos {
   // END = TSA_END_FACE / TSA_END_ANY (the kernels of tsa_align_batch_ends):
   // a cell that may end the path also folds its end key into the thread's
   // running best `end`, and the corner gives no score and no final states --
-  // the reduction of the keys does (align_end_reduce).
+  // the reduction of the keys does (align_end_reduce). With TB = false (the
+  // forward END form of align_grid_kernel.hip) the fold is all that is added.
+  // END = ALIGN_END_PTRS (its backward END form, TB = true): the pointer word
+  // alone, no fold and nothing at the corner -- the end is known by then, and
+  // the swept range may hold (la,lb,lc) without the path ending there.
   template <bool TB = true, int END = 0, class SymA>
   __device__ __forceinline__ void step(const uint4 *rd, uint4 *wr, int32_t ldz, int32_t q, int32_t la, int32_t y0,
                                        int32_t z0, int32_t lb, int32_t lc, uint32_t *cube, const KParams &kp,
@@ -175,11 +192,11 @@ struct AlignPos {
         S[SIZ] = max7_literal<SIZ, TB>(pr, kp, 0, sh, g);
         w |= g << (3 * SIZ);
         wr[idx] = pack7(S);
-        if constexpr (TB) {
-          cube[tb_index(x, y0 + y, z0 + z, la, cld)] = w;
-          if constexpr (END != 0) {
-            if (END == TSA_END_ANY || x == la || y0 + y == lb || z0 + z == lc) end->fold(S, x, y0 + y, z0 + z, lb, lc);
-          } else if (x == la && y0 + y == lb && z0 + z == lc) {  // FINAL_MAX, src/TriAlign_1cyc.v:141-142
+        if constexpr (TB) cube[tb_index(x, y0 + y, z0 + z, la, cld)] = w;
+        if constexpr (END > 0) {  // with or without pointers: the key is the cell's values alone
+          if (END == TSA_END_ANY || x == la || y0 + y == lb || z0 + z == lc) end->fold(S, x, y0 + y, z0 + z, lb, lc);
+        } else if constexpr (TB && END == 0) {
+          if (x == la && y0 + y == lb && z0 + z == lc) {  // FINAL_MAX, src/TriAlign_1cyc.v:141-142
             int32_t m = S[0];
 #pragma unroll
             for (int s = 1; s < NSTATE; ++s) m = max(m, S[s]);

@@ -2,7 +2,7 @@
 // "TriAlign Score: <n>" (src/TriAlign_tb.sv:339-341).
 //   tsa A.dat B.dat C.dat [--kernel auto|plane|pencil] [--device N]
 //       [--s3 rtl|sop] [--bits B] [--match M --mismatch X --go O --ge E]
-//       [--states] [--align [--end corner|face|any]] [--score-end face|any]
+//       [--states] [--align [--end corner|face|any] [--grid]] [--score-end face|any]
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -17,6 +17,8 @@ static int usage() {
           "           [--align]   (also print the optimal alignment; tsa_align_gpu)\n"
           "           [--end corner|face|any]   (with --align: where the path may end; face and any\n"
           "                                      go through tsa_align_batch_ends and print the end)\n"
+          "           [--grid]   (with --align: the grid path, for cubes whose pointers do not fit memory;\n"
+          "                       tsa_align_batch_grid, or tsa_align_batch_grid_ends with --end face|any)\n"
           "           [--score-end face|any]   (without --align: the end-free score and its end cell,\n"
           "                                     tsa_score_batch_ends; no alignment is traced. Its plan is\n"
           "                                     always the helix: with --kernel or --states a usage error)\n"
@@ -26,7 +28,7 @@ static int usage() {
 
 int main(int argc, char **argv) {
   const char *files[3];
-  int nf = 0, device = 0, kernel = TSA_KERNEL_AUTO, kernel_set = 0, states = 0, align = 0, end = TSA_END_CORNER, score_end = TSA_END_CORNER;
+  int nf = 0, device = 0, kernel = TSA_KERNEL_AUTO, kernel_set = 0, states = 0, align = 0, grid = 0, end = TSA_END_CORNER, score_end = TSA_END_CORNER;
   tsa_params p;
   tsa_default_params(&p);
   for (int i = 1; i < argc; ++i) {
@@ -46,6 +48,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(a, "--ge")) { const char *v = next(); if (!v) return usage(); p.gap_extend = atoi(v); }
     else if (!strcmp(a, "--states")) states = 1;
     else if (!strcmp(a, "--align")) align = 1;
+    else if (!strcmp(a, "--grid")) grid = 1;
     else if (!strcmp(a, "--end")) {
       const char *v = next();
       if (!v) return usage();
@@ -65,7 +68,7 @@ int main(int argc, char **argv) {
     else if (nf < 3) files[nf++] = a;
     else return usage();
   }
-  if (nf != 3 || (end != TSA_END_CORNER && !align)) return usage();
+  if (nf != 3 || ((end != TSA_END_CORNER || grid) && !align)) return usage();
   if (score_end != TSA_END_CORNER && (align || states || kernel_set)) return usage();
   uint8_t *s[3];
   int64_t n[3];
@@ -100,7 +103,7 @@ int main(int argc, char **argv) {
     uint8_t *mv = (uint8_t *)malloc((size_t)cap);
     int32_t nm = 0, st[3], en[3], sc = 0;
     if (!mv) rc = TSA_ENOMEM;
-    else if (end == TSA_END_CORNER)
+    else if (end == TSA_END_CORNER && !grid)
       rc = tsa_align_gpu(s[0], (int32_t)n[0], s[1], (int32_t)n[1], s[2], (int32_t)n[2], &p, &sc, mv, (int32_t)cap, &nm,
                          st, device);
     else {  // a batch of one: the three sequences back to back
@@ -108,7 +111,10 @@ int main(int argc, char **argv) {
       const int64_t off[4] = {0, n[0], n[0] + n[1], cap};
       if (seqs)
         for (int k = 0; k < 3; ++k) memcpy(seqs + off[k], s[k], (size_t)n[k]);
-      rc = seqs ? tsa_align_batch_ends(seqs, off, 1, &p, end, &sc, mv, &nm, st, en, device) : TSA_ENOMEM;
+      rc = !seqs                   ? TSA_ENOMEM
+           : !grid                 ? tsa_align_batch_ends(seqs, off, 1, &p, end, &sc, mv, &nm, st, en, device)
+           : end != TSA_END_CORNER ? tsa_align_batch_grid_ends(seqs, off, 1, &p, end, &sc, mv, &nm, st, en, device)
+                                   : tsa_align_batch_grid(seqs, off, 1, &p, &sc, mv, &nm, st, device);
       free(seqs);
     }
     if (rc) { fprintf(stderr, "tsa: %s (%d)\n", tsa_strerror(rc), rc); free(mv); return 1; }

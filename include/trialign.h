@@ -354,8 +354,10 @@ int tsa_align_batch_grid(const uint8_t *seqs, const int64_t *offsets, int32_t n,
  *
  * Not covered: the strip and grid paths, the plane sweep, tsa_align_gpu, a
  * device-resident form (tsa_align_rows_async works on uploaded results as it
- * is). The end-free score without a path is tsa_score_batch_ends below; the
- * prefixes it returns can be aligned on every traceback path. */
+ * is). A free end on the grid path, for cubes whose pointers do not fit the
+ * budget, is tsa_align_batch_grid_ends below. The end-free score without a
+ * path is tsa_score_batch_ends below; the prefixes it returns can be aligned on
+ * every traceback path. */
 #define TSA_END_CORNER 0
 #define TSA_END_FACE 1
 #define TSA_END_ANY 2
@@ -363,6 +365,42 @@ int tsa_align_batch_ends(const uint8_t *seqs, const int64_t *offsets, int32_t n,
                          const tsa_params *p, int32_t end_mode, int32_t *scores,
                          uint8_t *moves, int32_t *n_moves, int32_t *starts,
                          int32_t *ends, int32_t device);
+
+/* tsa_align_batch_ends with the larger triples on the grid path of
+ * tsa_align_batch_grid: the same signature and the same results for every
+ * triple, parameter set and end_mode, move for move. end_mode, scores, ends,
+ * starts, moves and n_moves, the tie rule, layouts, validation order, error
+ * codes (TSA_EINVAL for a null ends or an end_mode outside 0..2 included) and
+ * thread safety are tsa_align_batch_ends's. The plan, the tile geometry,
+ * align_tile, align_tb_bytes, chunking, TSA_ENOMEM and the per-triple need,
+ *   4*TY*(la+TZ-1)*TZ + 16*((nty-1)*la*(lc+1) + (ntz-1)*la*lb)  bytes,
+ * are tsa_align_batch_grid's: the end search takes nothing from the budget (8
+ * bytes per tile are allocated beside it).
+ *
+ * TSA_END_CORNER runs tsa_align_batch_grid's own path under every override and
+ * fills ends with the lengths. Under TSA_END_FACE and TSA_END_ANY, with
+ * align_mode unset or grid, a triple that fits one workgroup takes the resident
+ * kernel with its end search, as under tsa_align_batch_ends, and every other
+ * one the grid path: the forward launches sweep every tile, the last one
+ * included (d = 0 .. nty+ntz-2), each tile keeps the best end key of its
+ * cells, the largest of a triple's keys names the end cell, and the backward
+ * launches start from the tile of that cell, of which they sweep x <= x1. A set
+ * align_mode of resident or tiled holds, and the call is tsa_align_batch_ends;
+ * plane or strip returns TSA_EINVAL before any device work.
+ *
+ * A chunk queues [resident] + max (nty+ntz-1) forward + max (nty+ntz-1)
+ * backward counted launches (tsa_kernel_launch_count), the maxima over its grid
+ * triples: one forward launch more than tsa_align_batch_grid. The host does not
+ * know the end tile without a synchronisation, so the backward count is the
+ * worst case, whatever tile the path ends in; a workgroup whose triple's path
+ * has ended leaves before its first barrier.
+ *
+ * Not covered: the strip path, the plane sweep, tsa_align_gpu and a
+ * device-resident form (tsa_align_batch_async ends at the corner). */
+int tsa_align_batch_grid_ends(const uint8_t *seqs, const int64_t *offsets, int32_t n,
+                              const tsa_params *p, int32_t end_mode, int32_t *scores,
+                              uint8_t *moves, int32_t *n_moves, int32_t *starts,
+                              int32_t *ends, int32_t device);
 
 /* End-free scores without a path: scores[i] and ends[3i..3i+2] exactly as
  * tsa_align_batch_ends defines them (the same candidates per end_mode, the

@@ -30,8 +30,13 @@ must cost what the plain leg costs; face and any run the kernels that search
 the end cell as they sweep (resident and tiled only). Their results differ
 from the corner's by design, so only the corner leg joins the cross-check. A
 library without tsa_align_batch_ends (the parent of a comparison) skips them.
+The grid form's end legs go through tsa_align_batch_grid_ends
+(align_batch_ends(grid=True)); --core-tails makes triples whose end lies far
+from the corner: a shared first half and unrelated second halves.
   python tools/align_bench.py --n 512 --la 64 --forms resident --end corner,face,any
   python tools/align_bench.py --n 256 --la 128 --forms tiled --end corner,face,any
+  python tools/align_bench.py --n 256 --la 128 --forms grid,tiled --end corner,face,any
+  python tools/align_bench.py --n 8 --la 512 --forms grid --end corner,face,any --core-tails --tb-bytes 536870912
 A library without tsa_align_batch (an older build named by TSA_PKG_DIR) runs
 the loop alone: that is how the baseline of a comparison is taken.
 Prints one JSON line: per form the median, min and max of the passes in ms."""
@@ -53,6 +58,8 @@ def main():
     ap.add_argument("--lb", type=int, default=None)
     ap.add_argument("--lc", type=int, default=None)
     ap.add_argument("--related", action="store_true", help="related triples (B, C = mutated A), cubes only")
+    ap.add_argument("--core-tails", action="store_true",
+                    help="cubes whose sequences share their first half and have unrelated second halves")
     ap.add_argument("--passes", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--loop-n", type=int, default=None, help="triples of the align loop (default: all)")
@@ -73,6 +80,15 @@ def main():
     if args.related:
         trips = [synth.related_triple(900 + i, la) for i in range(args.n)]
         lb = lc = la
+    elif args.core_tails:
+        import numpy as np
+        lb = lc = la
+        trips = []
+        for i in range(args.n):
+            rng = np.random.default_rng(900 + i)
+            core = rng.integers(0, 4, la // 2).astype(np.uint8)
+            # a tail of one symbol per sequence, each its own: no tail symbol matches another sequence's tail
+            trips.append(tuple(np.concatenate([core, np.full(la - la // 2, k + 1, np.uint8)]) for k in range(3)))
     else:
         trips = [synth.triple(i, la, lb, lc) for i in range(args.n)]
     seqs, offs = tsa.pack_batch(trips)
@@ -94,6 +110,8 @@ def main():
             if args.tb_bytes is not None:
                 ov["align_tb_bytes"] = args.tb_bytes
             with tsa.overrides(**ov):
+                if mode == "grid":                   # tsa_align_batch_grid_ends
+                    return tsa.align_batch_ends(seqs=seqs, offsets=offs, end=end, grid=True)
                 return tsa.align_batch_ends(seqs=seqs, offsets=offs, end=end)
         return run
 
@@ -147,7 +165,7 @@ def main():
             if args.async_ and f != "plane" and hasattr(tsa, "align_batch_async"):
                 forms[f + "_async"], timers[f + "_async"] = device_leg(f)
             for e in filter(None, args.end.split(",")):
-                if hasattr(tsa, "align_batch_ends"):
+                if hasattr(tsa, "align_batch_ends") and (f != "grid" or "tsa_align_batch_grid_ends" in tsa.EXPORTS):
                     forms["%s_end_%s" % (f, e)] = batch_ends(f, e)
     out, refused = {}, {}
     for f, fn in list(forms.items()):                # first call: also the cross-check
@@ -173,7 +191,7 @@ def main():
             if k >= args.warmup:
                 times[f].append(dt)
     res = {"bench": "align", "n": args.n, "shape": [la, lb, lc], "related": bool(args.related),
-           "passes": args.passes, "warmup": args.warmup, "loop_n": loop_n, "forms_agree": same,
+           "core_tails": bool(args.core_tails), "passes": args.passes, "warmup": args.warmup, "loop_n": loop_n, "forms_agree": same,
            "version": tsa.version()}
     if args.tb_bytes is not None:
         res["tb_bytes"] = args.tb_bytes

@@ -41,11 +41,14 @@ from align_emu import DX, DY, DZ, ZERO, Cell
 from align_tiled_emu import POISON, tile_geom
 
 
-def _sweep(K, geom, ty, tz, xm, yrd, zrd, ywr, zwr, ptr):
+def _sweep(K, geom, ty, tz, xm, yrd, zrd, ywr, zwr, ptr, on_cell=None):
     """Tile (ty, tz) up to x = xm: reads the y face yrd and the z face zrd
     (None: zero), stores its last row into ywr and its last column into zwr
     (None: not kept), pointer words into ptr (None: the forward form) keyed
-    (x, local y, local z). Returns the cell (xm, lb, lc) if the tile holds it."""
+    (x, local y, local z). Returns the cell (xm, lb, lc) if the tile holds it.
+    on_cell(x, y, z, states, p) is called for every cell as the sweep computes
+    it, (y, z) global and p the number of its position in the tile
+    (tools/align_grid_ends_emu.py folds the end keys there)."""
     la, lb, lc = K.la, K.lb, K.lc
     TY, TZ, _, _ = geom
     y0, z0 = ty * TY, tz * TZ
@@ -64,6 +67,8 @@ def _sweep(K, geom, ty, tz, xm, yrd, zrd, ywr, zwr, ptr):
             out = K.step(h, x, rd[y][z], rd[y - 1][z], rd[y][z - 1], rd[y - 1][z - 1], y0 + y, z0 + z)
             if out:
                 new[(y, z)] = out[0]
+                if on_cell:
+                    on_cell(x, y0 + y, z0 + z, out[0], (y - 1) * tzl + (z - 1))
                 if ptr is not None:
                     ptr[(x, y, z)] = out[1]
                     if (x, y0 + y, z0 + z) == (xm, lb, lc):
