@@ -212,6 +212,38 @@ __device__ __forceinline__ void lds_w16_at(lds_u8 *base, int off, uint32_t v) {
 #ifndef TSA_DMA_SADDR
 #define TSA_DMA_SADDR 1
 #endif
+// The forms TSA_REC_PREV applies to: wave 0 issues no ring fetch. A
+// global_load_lds lands in LDS whichever wave issues it, so waves 1 and 2 issue
+// the rows with dma16x2_saddr, at the first and the third step of the four-step
+// group (static steps: no run-time test in the loop), and wave 0 only reads its
+// xr0 slots. At such a step t wave 1 issues the row of step t + 6, wave 2 that
+// of step t + 7. The step barrier is the only synchronisation: the row of step
+// s + PD goes into slot s % PD in the barrier interval after the one in which
+// wave 0 read step s there, and at the step after an issue the issuer waits
+// with a counted vmcnt until only its two newest rows are in flight, before the
+// barrier that precedes the interval of the oldest one's step. Issue to use is
+// 5 to 6 steps. The issuers start PD steps before wave 0's switch step t_sw, so
+// they fill the pipeline too and nothing is primed. 0: wave 0 fetches its own
+// rows, PD steps ahead. Every pass of eight above every pass of the parent
+// together with TSA_BINJ_SGPR and TSA_RING_ST_SADDR, +1.2 and +1.7 % on two
+// boxes; alone +0.4 %, not resolved (profiles/r10_helix_fetch_ab.jsonl). Four
+// issuers with a row per group each, and wave 1 issuing all four rows, measured
+// slower than two and were not kept.
+#ifndef TSA_FETCH_SHARED
+#define TSA_FETCH_SHARED 1
+#endif
+// The forms TSA_REC_PREV applies to, last wave: the ring store's address as the
+// row's uniform base plus the lane's unsigned 32-bit offset, which the compiler
+// selects as the store's saddr form (0: a 64-bit VALU address per step)
+#ifndef TSA_RING_ST_SADDR
+#define TSA_RING_ST_SADDR 1
+#endif
+// The forms TSA_REC_PREV applies to: the x = 1 position's B code injected from
+// the SGPR it lives in (vbfi_s), as the H values are (0: through a VGPR operand,
+// which costs a v_mov per step)
+#ifndef TSA_BINJ_SGPR
+#define TSA_BINJ_SGPR 1
+#endif
 // (only s_mov in the statement: an s_add would write SCC behind the compiler's back)
 __device__ __forceinline__ void dma16x2_saddr(const uint8_t *sbase, uint32_t voff0, uint32_t voff1,
                                               uint32_t lds0, uint32_t lds1) {
@@ -517,7 +549,7 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
   // lap-wrap update has set it). Exec-masked single-lane writes: no per-lane
   // offset VGPRs (the kernel sits at the 128-VGPR edge of 4 waves per SIMD).
   lds_u8 *wrH = to_lds(xr + w * HNSL * SLOT_BYTES + 10);  // lane 0's pair-0 Iyz high half
-  const uint32_t own = (uint32_t)lane * REC_BYTES;        // the lane's record in a ring row
+  uint32_t own = (uint32_t)lane * REC_BYTES;              // the lane's record in a ring row
   const int32_t nunit = TWO ? (n + 1) / 2 : n;  // workgroup units: triples, or pairs
   for (int unit = blockIdx.x; unit < nunit; unit += gridDim.x) {
     const int tri = TWO ? 2 * unit : unit;
@@ -566,6 +598,9 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
     // workspace may hold anything (an earlier unit's or launch's rows) at entry
     constexpr bool FIRSTLAP = VS && TSA_RING_FIRSTLAP;
     const int32_t t_sw = FIRSTLAP ? max(lag - PD, 0) & ~3 : 0;
+    // SF (TSA_FETCH_SHARED): middle waves issue wave 0's ring fetches. (M = 2:
+    // P >= 256, so lag >= 242 and t_sw >= 2 PD: the issuers' first groups exist)
+    constexpr bool SF = RP && FIRSTLAP && TSA_FETCH_SHARED && TSA_DMA_SADDR && PD == 8 && NW >= 4;
     if constexpr (FIRSTLAP) {
       // row 0's face cells as wave 0 meets them at step tr: x + z = tr + 2 for
       // every position ({Iy, Ixy, Iyz, best} = lam q - lam, lam q x 3); step tr
@@ -761,6 +796,20 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
     if constexpr (!FIRSTLAP) {
       if (w == 0) prime(0);
     }
+    // SF: issuer w (1 or 2) takes the rows of the steps = iss_j (mod 2). It issues
+    // from group t_iss on, at step t the row of step t + 6 + iss_j; the first row
+    // wave 0 reads is the second it issues (the very first, of step t_sw - 2 +
+    // iss_j, lands in a slot nobody reads). The other waves never get there.
+    const int32_t iss_j = w - 1;
+    int32_t t_iss = 0x7FFFFFFF;
+    if constexpr (SF) {
+      if (w == 1 || w == 2) {
+        t_iss = t_sw - PD;
+        dma_row = ((t_iss + 6 + iss_j - lag) % R + R) % R;
+      }
+    }
+    // byte offset of step (6 + iss_j)'s slot; step t's issue adds t slots (mod PD)
+    const uint32_t iss_slot0 = (uint32_t)((6 + iss_j) * SLOT_BYTES);
     const uint32_t dvo0 = (uint32_t)lane * REC_BYTES, dvo1 = dvo0 + PAIR_BYTES;  // TSA_DMA_SADDR
     const uint32_t xr0_lds = __builtin_amdgcn_readfirstlane(
         (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)xr0);
@@ -836,6 +885,11 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
       constexpr bool L1 = (decltype(role)::value >> 4) & 1;  // HT: the loop's lam = 1 version
       constexpr int ISC = (M == 2 && WPAR >= 0) ? (HSK == 2 ? PH : PH ^ WPAR) : -1;
       constexpr bool FIN = decltype(fin_step)::value;  // the last step (t == T-1)
+      // SF: this wave issues ring rows in this loop (role bit 5): at the even
+      // steps; the odd step after waits for the oldest row before its barrier
+      constexpr bool ISS = SF && ((decltype(role)::value >> 5) & 1) && TSA_ABL_RING != 1 && TSA_ABL_RING != 3;
+      constexpr bool ISS_AT = ISS && PQ >= 0 && PQ < 4 && (PQ & 1) == 0;
+      constexpr bool ISS_WAIT = ISS && PQ >= 0 && PQ < 4 && (PQ & 1) == 1;
       // this step's A codes (LDS table) and the B code of position x = 1
       uint32_t a[M];
       if constexpr (TSA_A_PREFETCH) {
@@ -866,7 +920,8 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
         // the slot of step t is (t % PD): r0_own / r0_prev hold the group's part
         // (PD = 8, two groups), the step's is a constant offset
         static_assert(!RP || PD == 8, "TSA_REC_PREV: wave 0's slots as two groups of four");
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(M * (PD - 1)) : "memory");
+        // (SF: the issuer waited for the row before the barrier this step follows)
+        if constexpr (!SF) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(M * (PD - 1)) : "memory");
         read_prev(r0_own, r0_prev, (PQ & 3) * SLOT_BYTES);
       } else if constexpr (ROLE == 0) {
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(M * (PD - 1)) : "memory");
@@ -947,7 +1002,9 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
               inIxz[i] = vbfi(m1, fpv, inIxz[i]);
               inM[i] = vbfi(m1, zero, inM[i]);
             }
-            b[i] = vbfi(m1, binj, b[i]);
+            // (RP forms: binj is wave-uniform and lives in an SGPR; the bfi reads it there)
+            if constexpr (RP && TSA_BINJ_SGPR) b[i] = vbfi_s(m1, binj, b[i]);
+            else b[i] = vbfi(m1, binj, b[i]);
             if constexpr (F16) {  // the new row's per-row terms
 #if TSA_ROW_NEXT
               SBC[i] = vbfi(m1, SBCn[i], SBC[i]);
@@ -1049,8 +1106,15 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
         }
         if constexpr (TSA_ABL_RING == 1 || TSA_ABL_RING == 2) {
         } else if constexpr (!SHR) {
+          // a uniform row base plus the lane's unsigned 32-bit offset: the store's
+          // saddr form, no 64-bit VALU address per step (the offset is named in
+          // the step, or its 64-bit extension is hoisted out of the loop and the
+          // add of the row base comes back)
+          if constexpr (RP && TSA_RING_ST_SADDR) asm volatile("" : "+v"(own));
           uint4 *dst = (uint4 *)__builtin_assume_aligned(
-              ring + (int64_t)st_row * SLOT_BYTES + lane * REC_BYTES, 16);
+              RP && TSA_RING_ST_SADDR ? (ring + (int64_t)st_row * SLOT_BYTES) + own
+                                      : ring + (int64_t)st_row * SLOT_BYTES + lane * REC_BYTES,
+              16);
 #pragma unroll
           for (int i = 0; i < M; ++i) {
             if constexpr (TSA_RING_NT & 1) {
@@ -1244,7 +1308,15 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
       }
 
       // ---- wave 0: fetch the record of step t + PD into the slot just consumed
-      if constexpr (ROLE == 0 && TSA_ABL_RING != 1 && TSA_ABL_RING != 3) {
+      if constexpr (ISS_AT) {  // SF: the row of step t + 6 + iss_j, into that step's slot
+        const uint32_t slot = ((uint32_t)t * SLOT_BYTES + iss_slot0) & (uint32_t)(PD * SLOT_BYTES - 1);
+        dma16x2_saddr(ring + (int64_t)dma_row * SLOT_BYTES, dvo0, dvo1, xr0_lds + slot, xr0_lds + slot + PAIR_BYTES);
+        dma_row += 2;
+        if (dma_row >= R) dma_row -= R;
+      }
+      // the two rows issued after the one now due stay in flight (M loads a row)
+      if constexpr (ISS_WAIT) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * M) : "memory");
+      if constexpr (ROLE == 0 && !SF && TSA_ABL_RING != 1 && TSA_ABL_RING != 3) {
 #pragma unroll
         for (int i = 0; i < M; ++i)
           if constexpr (TSA_DMA_SADDR && M == 2) {
@@ -1320,15 +1392,30 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
             TSA_INLINE_IF_WIDE(step(Q2, first, t + 2, mid));
             TSA_INLINE_IF_WIDE(step(Q3, first, t + 3, mid));
           }
-          if (t < T) prime(t);
+          if constexpr (!SF) {
+            if (t < T) prime(t);
+          }
         }
 #pragma unroll 1
-        for (; t < T; t += 4) {
+        for (; t < (SF && (decltype(role)::value & 3) == 1 ? min(t_iss, T) : T); t += 4) {
           group_bases();
           TSA_INLINE_IF_WIDE(step(Q0, role, t, mid));
           TSA_INLINE_IF_WIDE(step(Q1, role, t + 1, mid));
           TSA_INLINE_IF_WIDE(step(Q2, role, t + 2, mid));
           TSA_INLINE_IF_WIDE(step(Q3, role, t + 3, mid));
+        }
+        if constexpr (SF && (decltype(role)::value & 3) == 1) {
+          // the issuers' groups from t_iss on: the same steps with the fetch
+          // statements (a middle wave that issues nothing has left the loop above at T)
+          constexpr std::integral_constant<int, decltype(role)::value | 32> issuing{};
+#pragma unroll 1
+          for (; t < T; t += 4) {
+            group_bases();
+            TSA_INLINE_IF_WIDE(step(Q0, issuing, t, mid));
+            TSA_INLINE_IF_WIDE(step(Q1, issuing, t + 1, mid));
+            TSA_INLINE_IF_WIDE(step(Q2, issuing, t + 2, mid));
+            TSA_INLINE_IF_WIDE(step(Q3, issuing, t + 3, mid));
+          }
         }
         return;
       }

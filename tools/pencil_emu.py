@@ -57,6 +57,24 @@ messages). V-space values are shifted by lam (x + y + z). These are what
 pencil_slack (csrc/pencil_kernel.hip) has to cover around the candidate range
 (tests/test_range_proof.py). Without the key nothing is recorded.
 
+`shared_fetch=True` (V-space with `read_prev`, M = 2; the kernel's
+TSA_FETCH_SHARED) replays who fetches wave 0's ring rows and when. Wave 0 reads
+step t's row from slot t mod PD of its LDS ring copy (xr0) and issues nothing;
+waves 1 and 2 issue at the first and the third step t of every four-step group,
+from PD steps before t_sw on, the row of step t + 6 (wave 1) or t + 7 (wave 2)
+into that step's slot. A slot is IN FLIGHT, its contents undefined, from the
+step its fetch is issued until the issuing wave's counted wait (at the step
+after an issue: all but its two newest rows have landed) and the barrier that
+follows. The step barrier (after every odd step) is the only order between
+waves, so two things in one barrier interval are unordered. Two events are
+counted into `events`: "fetch_in_flight", wave 0 reading a slot that is in
+flight or does not hold its step's row, and "fetch_unread", a fetch issued
+into a slot whose row wave 0 has not read before the interval's opening
+barrier (or that is itself still in flight). Either leaves garbage in the
+record wave 0 reads. `fetch_shift=k` moves every fetch k barrier intervals
+EARLIER (k < 0: later) than the kernel's schedule: the test hook that shows
+both rules bite.
+
 Layout as in the kernel: NW = 8 waves, wave w owns row y = lap*NW + w + 1;
 lane l, register i, half h is position k = 64M h + M l + i (TWO mode, LC <= 64
 and M = 1: k = l, and half h scores its own triple); position k of wave w
@@ -162,7 +180,7 @@ def end_reduce(keys, lc):
 
 def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shifted=None, garbage_seed=None,
             ring_garbage_seed=None, read_prev=False, int_bits=False, bias=None, events=None, end=None,
-            max_lens=None):
+            max_lens=None, shared_fetch=False, fetch_shift=0):
     """Scores of one workgroup's unit: one triple, or two (TWO mode: LC <= 64).
     Returns a list of scores (one per triple). `garbage_seed` starts the LDS
     record slots, `ring_garbage_seed` the global ring, with garbage (what an
@@ -270,6 +288,40 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
         for slot, v in ((2, lam * 1), (3, lam * 2)):
             xr[0, slot, 2, 0, 0, :] = v
             xr[0, slot, 3, 0, 0, :] = v
+    # shared_fetch: wave 0's LDS copy of the ring rows, slot by slot
+    assert (not shared_fetch or (vs and read_prev and M == 2 and not two))
+    if shared_fetch:  # (the other modes' callers compare the dict they get back)
+        events.setdefault("fetch_in_flight", 0)
+        events.setdefault("fetch_unread", 0)
+    sf_rng = np.random.default_rng(0x5F)
+    sf_garbage = lambda: sf_rng.integers(*((0, 1 << 16) if int_bits else (-3000, 3000)), (4,) + shape)
+    xr0 = [dict(step=None, flying=False, data=sf_garbage()) for _ in range(PD)]
+    sf_queue = {w: [] for w in ((1, 2) if shared_fetch else ())}  # issuer -> its rows in flight, oldest first
+
+    def sf_step(t):  # after every wave's step t: the issues, then the waits (and what lands at the barrier)
+        for w, queue in sf_queue.items():
+            issuing = t >= t_sw - PD
+            if issuing and not t & 1:
+                s_row = t + 6 + (w - 1) + 2 * fetch_shift
+                slot = xr0[s_row % PD]
+                if slot["flying"] or (slot["step"] is not None and slot["step"] >= t_sw and slot["step"] < T
+                                      and t // 2 <= slot["step"] // 2):
+                    events["fetch_unread"] += 1
+                slot.update(step=s_row, flying=True, data=sf_garbage())
+                queue.append((s_row, ring[(s_row - lag) % R].copy()))
+            if issuing and t & 1:  # the counted wait before this (odd) step's barrier
+                while len(queue) > 2:
+                    s_row, data = queue.pop(0)
+                    if xr0[s_row % PD]["step"] == s_row:  # (not overwritten by a later fetch)
+                        xr0[s_row % PD].update(flying=False, data=data)
+
+    def sf_read(t):  # wave 0's record of step t >= t_sw
+        slot = xr0[t % PD]
+        if slot["flying"] or slot["step"] != t:
+            events["fetch_in_flight"] += 1
+            return sf_garbage()
+        return slot["data"]
+
     st = []
     for w in range(NW):
         xpos0 = (P - (S * w) % P) % P
@@ -325,7 +377,7 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
                                 enc(d["H"][t + 1])])[:, None, None, None] * \
                     np.ones((1,) + shape, np.int64)
             else:
-                rec = ring[(t - lag) % R] if w == 0 else xr[w - 1, (t - S) & 3]
+                rec = (sf_read(t) if shared_fetch else ring[(t - lag) % R]) if w == 0 else xr[w - 1, (t - S) & 3]
             u = (t - S * w - kpos) % P
             acode = per_half(lambda tr, h: code(tr[0], u))
             if track is not None:  # the halves that hold a real cell (x <= LA, y <= LB, z <= LC) at this step
@@ -505,6 +557,8 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
         for w in range(NW):
             xr[w, t & 3] = outs[w]
         ring[t % R] = outs[NW - 1]
+        if shared_fetch:
+            sf_step(t)
     if end_modes:
         events["end_key"] = {m: end_reduce(ekeys[m], len(triples[0][2])) for m in end_modes}
         return [end_decode(events["end_key"][m]) for m in end_modes]
