@@ -68,6 +68,8 @@ EXPORTS = (
     "tsa_align_batch_grid", "tsa_align_workspace_size", "tsa_align_batch_async", "tsa_align_rows_async",
     "tsa_align_batch_ends", "tsa_score_batch_ends", "tsa_score_ends_workspace_size",
     "tsa_score_batch_ends_async", "tsa_describe_score_ends_plan", "tsa_align_batch_grid_ends",
+    "tsa_score_batch_ends_ex", "tsa_score_ends_workspace_size_ex", "tsa_score_batch_ends_async_ex",
+    "tsa_describe_score_ends_plan_ex",
 )
 
 # Plan overrides the library accepts (tsa_set_override; include/trialign.h).
@@ -173,6 +175,15 @@ def _load_lib() -> ctypes.CDLL:
         [pp, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     lib.tsa_describe_score_ends_plan.argtypes = [ctypes.c_int32] * 4 + [pp, ctypes.c_int32, ctypes.c_char_p,
                                                                        ctypes.c_size_t]
+    lib.tsa_score_batch_ends_ex.argtypes = [u8p, i64p, ctypes.c_int32, pp, ctypes.c_int32, ctypes.c_int32, i32p, i32p,
+                                            ctypes.c_int32]
+    lib.tsa_score_ends_workspace_size_ex.argtypes = [ctypes.c_int32] * 4 + [pp, ctypes.c_int32, ctypes.c_int32,
+                                                                           ctypes.POINTER(ctypes.c_size_t)]
+    lib.tsa_score_batch_ends_async_ex.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int32] * 4 + \
+        [pp, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+         ctypes.c_void_p]
+    lib.tsa_describe_score_ends_plan_ex.argtypes = [ctypes.c_int32] * 4 + [pp, ctypes.c_int32, ctypes.c_int32,
+                                                                          ctypes.c_char_p, ctypes.c_size_t]
     szp = ctypes.POINTER(ctypes.c_size_t)
     lib.tsa_align_workspace_size.argtypes = [i64p, ctypes.c_int32, pp, ctypes.c_int32, szp, szp]
     lib.tsa_align_batch_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, i64p, ctypes.c_int32, pp,
@@ -207,7 +218,8 @@ def _load_lib() -> ctypes.CDLL:
                  "tsa_align_batch_lowmem", "tsa_align_batch_grid", "tsa_align_workspace_size",
                  "tsa_align_batch_async", "tsa_align_rows_async", "tsa_align_batch_ends", "tsa_score_batch_ends",
                  "tsa_score_ends_workspace_size", "tsa_score_batch_ends_async", "tsa_describe_score_ends_plan",
-                 "tsa_align_batch_grid_ends"):
+                 "tsa_align_batch_grid_ends", "tsa_score_batch_ends_ex", "tsa_score_ends_workspace_size_ex",
+                 "tsa_score_batch_ends_async_ex", "tsa_describe_score_ends_plan_ex"):
         getattr(lib, name).restype = ctypes.c_int
     return lib
 
@@ -510,8 +522,13 @@ def _end_mode(end, what: str) -> int:
     return int(mode)
 
 
+def _ends_kernel(kernel) -> int:
+    return KERNELS[kernel] if isinstance(kernel, str) else int(kernel)
+
+
 def score_batch_ends(triples=None, params: Optional[TsaParams] = None, end: str | int = "any", device: int = 0,
-                     seqs: Optional[np.ndarray] = None, offsets: Optional[np.ndarray] = None) -> list:
+                     seqs: Optional[np.ndarray] = None, offsets: Optional[np.ndarray] = None,
+                     kernel: str | int | None = None) -> list:
     """End-free scores without a path (tsa_score_batch_ends): a list of
     ``(score, (x1, y1, z1))``, one per triple -- the score and end cell
     ``align_batch_ends`` returns for the same ``end``, computed by the helix
@@ -519,7 +536,15 @@ def score_batch_ends(triples=None, params: Optional[TsaParams] = None, end: str 
     alignment of ``a[:x1], b[:y1], c[:z1]``: screen here, then ``align_batch``
     (any path) the prefixes of the hits. ``"face"`` and ``"any"`` need a cube
     the factored f16-class helix scores with max_lc <= 256 and max_lb <= 2048;
-    anything else raises ``TsaError(TSA_ERANGE)``."""
+    anything else raises ``TsaError(TSA_ERANGE)``.
+
+    ``kernel`` (tsa_score_batch_ends_ex): ``None`` is the call above;
+    ``"plane"`` runs the end search of the literal helix, in the RTL's wrapped
+    arithmetic, for any parameter set (max_la <= 4095, max_lb <= 4096,
+    max_lc <= 256); ``"auto"`` takes the factored helix where it admits the
+    request and the literal one otherwise, so it returns ``align_batch_ends``'s
+    score and end for every parameter set within that shape; ``"pencil"`` is
+    the call above."""
     mode = _end_mode(end, "score_batch_ends")
     p = params or TsaParams.default()
     if seqs is None:
@@ -529,17 +554,30 @@ def score_batch_ends(triples=None, params: Optional[TsaParams] = None, end: str 
     n = (len(offsets) - 1) // 3
     sc = np.zeros(max(n, 1), dtype=np.int32)
     en = np.zeros(max(3 * n, 1), dtype=np.int32)
-    rc = _lib.tsa_score_batch_ends(_ptr(seqs, ctypes.c_uint8), _ptr(offsets, ctypes.c_int64), n, ctypes.byref(p),
-                                   mode, _ptr(sc, ctypes.c_int32), _ptr(en, ctypes.c_int32), device)
-    _check(rc, "tsa_score_batch_ends")
+    if kernel is None:
+        rc = _lib.tsa_score_batch_ends(_ptr(seqs, ctypes.c_uint8), _ptr(offsets, ctypes.c_int64), n, ctypes.byref(p),
+                                       mode, _ptr(sc, ctypes.c_int32), _ptr(en, ctypes.c_int32), device)
+        _check(rc, "tsa_score_batch_ends")
+    else:
+        rc = _lib.tsa_score_batch_ends_ex(_ptr(seqs, ctypes.c_uint8), _ptr(offsets, ctypes.c_int64), n,
+                                          ctypes.byref(p), mode, _ends_kernel(kernel), _ptr(sc, ctypes.c_int32),
+                                          _ptr(en, ctypes.c_int32), device)
+        _check(rc, "tsa_score_batch_ends_ex")
     return [(s, tuple(e)) for s, e in zip(sc[:n].tolist(), en[:3 * n].reshape(-1, 3).tolist())]
 
 
 def score_ends_workspace_size(n: int, max_la: int, max_lb: int, max_lc: int, params: Optional[TsaParams] = None,
-                              end: str | int = "any") -> int:
-    """Bytes of workspace ``score_batch_ends_async`` needs (tsa_score_ends_workspace_size)."""
+                              end: str | int = "any", kernel: str | int | None = None) -> int:
+    """Bytes of workspace ``score_batch_ends_async`` needs (tsa_score_ends_workspace_size;
+    with a ``kernel``, tsa_score_ends_workspace_size_ex)."""
     p = params or TsaParams.default()
     sz = ctypes.c_size_t(0)
+    if kernel is not None:
+        _check(_lib.tsa_score_ends_workspace_size_ex(n, max_la, max_lb, max_lc, ctypes.byref(p),
+                                                     _end_mode(end, "score_ends_workspace_size"),
+                                                     _ends_kernel(kernel), ctypes.byref(sz)),
+               "tsa_score_ends_workspace_size_ex")
+        return int(sz.value)
     _check(_lib.tsa_score_ends_workspace_size(n, max_la, max_lb, max_lc, ctypes.byref(p),
                                               _end_mode(end, "score_ends_workspace_size"), ctypes.byref(sz)),
            "tsa_score_ends_workspace_size")
@@ -548,10 +586,20 @@ def score_ends_workspace_size(n: int, max_la: int, max_lb: int, max_lc: int, par
 
 def score_batch_ends_async(d_seqs_ptr: int, d_offsets_ptr: int, n: int, max_la: int, max_lb: int, max_lc: int,
                            d_scores_ptr: int, d_ends_ptr: int, d_ws_ptr: int, ws_bytes: int, stream_ptr: int = 0,
-                           params: Optional[TsaParams] = None, end: str | int = "any") -> None:
-    """Device-resident ``score_batch_ends`` (tsa_score_batch_ends_async): raw
-    device addresses, results (n scores, 3n ends, int32) stay on the device."""
+                           params: Optional[TsaParams] = None, end: str | int = "any",
+                           kernel: str | int | None = None) -> None:
+    """Device-resident ``score_batch_ends`` (tsa_score_batch_ends_async; with a
+    ``kernel``, tsa_score_batch_ends_async_ex): raw device addresses, results
+    (n scores, 3n ends, int32) stay on the device."""
     p = params or TsaParams.default()
+    if kernel is not None:
+        rc = _lib.tsa_score_batch_ends_async_ex(
+            ctypes.c_void_p(d_seqs_ptr), ctypes.c_void_p(d_offsets_ptr), n, max_la, max_lb, max_lc, ctypes.byref(p),
+            _end_mode(end, "score_batch_ends_async"), _ends_kernel(kernel), ctypes.c_void_p(d_scores_ptr),
+            ctypes.c_void_p(d_ends_ptr), ctypes.c_void_p(d_ws_ptr), ctypes.c_size_t(ws_bytes),
+            ctypes.c_void_p(stream_ptr))
+        _check(rc, "tsa_score_batch_ends_async_ex")
+        return
     rc = _lib.tsa_score_batch_ends_async(ctypes.c_void_p(d_seqs_ptr), ctypes.c_void_p(d_offsets_ptr), n, max_la,
                                          max_lb, max_lc, ctypes.byref(p), _end_mode(end, "score_batch_ends_async"),
                                          ctypes.c_void_p(d_scores_ptr), ctypes.c_void_p(d_ends_ptr),
@@ -561,12 +609,20 @@ def score_batch_ends_async(d_seqs_ptr: int, d_offsets_ptr: int, n: int, max_la: 
 
 
 def describe_score_ends_plan(n: int, max_la: int, max_lb: int, max_lc: int, params: Optional[TsaParams] = None,
-                             end: str | int = "any") -> str:
+                             end: str | int = "any", kernel: str | int | None = None) -> str:
     """The plan ``score_batch_ends`` runs (tsa_describe_score_ends_plan; host-only):
     the helix plan with ``ends=face`` or ``ends=any``, or ``describe_plan``'s text
-    for the corner. Raises ``TsaError`` with the code the scoring call would return."""
+    for the corner. Raises ``TsaError`` with the code the scoring call would return.
+    With a ``kernel`` (tsa_describe_score_ends_plan_ex) the literal end search reads
+    ``plane literal-helix M=.. P=.. ends=..``."""
     p = params or TsaParams.default()
     buf = ctypes.create_string_buffer(512)
+    if kernel is not None:
+        _check(_lib.tsa_describe_score_ends_plan_ex(n, max_la, max_lb, max_lc, ctypes.byref(p),
+                                                    _end_mode(end, "describe_score_ends_plan"),
+                                                    _ends_kernel(kernel), buf, len(buf)),
+               "tsa_describe_score_ends_plan_ex")
+        return buf.value.decode()
     _check(_lib.tsa_describe_score_ends_plan(n, max_la, max_lb, max_lc, ctypes.byref(p),
                                              _end_mode(end, "describe_score_ends_plan"), buf, len(buf)),
            "tsa_describe_score_ends_plan")

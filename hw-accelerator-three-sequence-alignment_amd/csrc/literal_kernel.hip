@@ -187,7 +187,24 @@ __device__ __forceinline__ void push_literal(const LitArgs &c, uint32_t ones, ui
 //      sA2 [P+ZT] u32          A codes (1 << s) of positions k (lo) and k+64M (hi)
 //      sB  [LB+1] u32          B code, both halves
 //      fin [7][M][64] u32      the final cell's states (wave w_f)
-template <int M, bool SOP>
+//
+// END: the end-free score (tsa_score_batch_ends_ex): every step folds the MAX7
+// of each real cell's seven states into the position's key (lit_end_fold,
+// pencil_common.h); after the loop the keys are reduced over
+// the wave and the workgroup, and thread 0 writes scores[tri] and, through the
+// final7 argument, ends[3 tri ..] = (x1, y1, z1). No corner capture.
+
+// The end search's per-lane state: the running key and its lap for each
+// position (v / lap [i][h]: half h of register i) and the lane's first
+// position. Empty unless END, as pencil_kernel's EndKeys.
+template <int M, bool END>
+struct LitEndKeys {
+  uint32_t v[M][2], lap[M][2], kl;
+};
+template <int M>
+struct LitEndKeys<M, false> {};
+
+template <int M, bool SOP, bool END = false>
 __global__ __launch_bounds__(64 * LIT_NW) void literal_kernel(
     const uint8_t *__restrict__ seqs, const int64_t *__restrict__ offs, int32_t n, int32_t P, int32_t R,
     int32_t lds_a, int32_t lds_b, int64_t ring_stride, uint8_t *__restrict__ ring_base,
@@ -283,6 +300,12 @@ __global__ __launch_bounds__(64 * LIT_NW) void literal_kernel(
         shIxz[1][i] = fxz;
         svM[1][i] = fm;
       }
+    }
+    LitEndKeys<M, END> ek;
+    if constexpr (END) {
+      ek.kl = (uint32_t)(M * lane);
+#pragma unroll
+      for (int i = 0; i < M; ++i) ek.v[i][0] = ek.v[i][1] = ek.lap[i][0] = ek.lap[i][1] = 0u;
     }
     int32_t xpos0 = (P - ((S * w) % P)) % P;  // position at x' = 0 at step t
     int32_t lap0 = w == 0 ? 0 : -1;
@@ -388,8 +411,24 @@ __global__ __launch_bounds__(64 * LIT_NW) void literal_kernel(
       }
 #pragma unroll
       for (int i = 0; i < M; ++i) asm volatile("" : "+v"(bn[i]));
+      // ---- END: fold the MAX7 of this step's real cells into the positions'
+      // keys. Position k is at x = xpos0 - k of row lap0 NW + w + 1 once it has
+      // wrapped (class A), at x = xpos0 + P - k of the row NW above otherwise
+      // (class B); each class's terms are wave-uniform (lit_end_class). A lap
+      // of -1 (a wave before its first wrap, the last wave's unstarted
+      // positions), rows past lb, x = 0 and x > la are in neither class.
+      if constexpr (END) {
+        const LitEndClass eA = lit_end_class(ca.end_face, xpos0, lap0, lap0 * NW + w, la, lb);
+        const LitEndClass eB = lit_end_class(ca.end_face, xpos0 + P, lap0 - 1, (lap0 - 1) * NW + w, la, lb);
+#pragma unroll
+        for (int i = 0; i < M; ++i) {
+          const uint32_t best = mx2(mx2(mx2(MM[i], X[i]), mx2(Y[i], Z[i])), mx2(mx2(XY[i], YZ[i]), XZ[i]));
+          if (ca.end_face) lit_end_fold<M, true>(best, ek.kl + i, (uint32_t)(lc - 1), eA, eB, ek.v[i], ek.lap[i]);
+          else lit_end_fold<M, false>(best, ek.kl + i, (uint32_t)(lc - 1), eA, eB, ek.v[i], ek.lap[i]);
+        }
+      }
       // the final cell's states (src/TriAlign_1cyc.v:130,138,141-142)
-      if (t == t_f && w == w_f) {
+      if (!END && t == t_f && w == w_f) {
 #pragma unroll
         for (int i = 0; i < M; ++i) {
           fin[(0 * M + i) * 64 + lane] = MM[i];
@@ -501,8 +540,42 @@ __global__ __launch_bounds__(64 * LIT_NW) void literal_kernel(
     else if (w == NW - 1) run(std::integral_constant<int, 2 + 8>{});
     else if (w & 1) run(std::integral_constant<int, 1 + 8>{});
     else run(std::integral_constant<int, 1 + 4>{});
+    if constexpr (END) {
+      // z, the lap and the wave's row join the key: {score : ~(x-1)} : ~y : ~z, so
+      // the largest is the best score at the smallest x, then y, then z.
+      // Positions past lc (padding in z) never enter. A wave reduce, then fin[2 w ..].
+      uint64_t bk = 0;
+#pragma unroll
+      for (int i = 0; i < M; ++i)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int32_t k = M * lane + i + 64 * M * h;
+          const uint32_t key = ek.v[i][h];
+          if (k < lc && key != 0u) bk = umax64(bk, lit_end_key64(key, ek.lap[i][h], (uint32_t)w, NW, (uint32_t)k));
+        }
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) bk = umax64(bk, (uint64_t)__shfl_xor((unsigned long long)bk, o, 64));
+      if (lane == 0) {
+        fin[2 * w] = (uint32_t)bk;
+        fin[2 * w + 1] = (uint32_t)(bk >> 32);
+      }
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    if constexpr (END) {
+      if (threadIdx.x == 0) {
+        uint64_t bk = 0;
+        for (int j = 0; j < NW; ++j) bk = umax64(bk, ((uint64_t)fin[2 * j + 1] << 32) | fin[2 * j]);
+        const uint32_t top = (uint32_t)(bk >> 32);  // {half ^ 0x8000 : 4095 - (x - 1)}
+        int32_t *ends = final7;
+        scores[tri] = (int32_t)(int16_t)(uint16_t)((top >> 16) ^ 0x8000u) >> ca.sh;
+        ends[3 * (int64_t)tri] = (int32_t)(4095u - (top & 0xFFFFu)) + 1;
+        ends[3 * (int64_t)tri + 1] = (int32_t)(0xFFFFu - (((uint32_t)bk >> 16) & 0xFFFFu));
+        ends[3 * (int64_t)tri + 2] = (int32_t)(0xFFFFu - ((uint32_t)bk & 0xFFFFu));
+      }
+      __syncthreads();
+      continue;
+    }
     if (threadIdx.x < 7) {  // unshift the final cell's states
       int32_t l_f, i_f, h_f;
       pos_split<M>(k_f, l_f, i_f, h_f);
@@ -570,12 +643,12 @@ LitArgs lit_args(const KParams &kp) {
   return c;
 }
 
-template <int M, bool SOP>
+template <int M, bool SOP, bool END = false>
 static int launch_lit(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, int32_t max_lb,
                       const LitGeom &g, int32_t *d_scores, int32_t *d_final7, void *d_ws, const LitArgs &ca,
                       hipStream_t stream) {
   const int32_t lds_a = 4 * (g.P + 128 * M), lds_b = 4 * ((max_lb + 4) & ~3);
-  auto kfn = literal_kernel<M, SOP>;
+  auto kfn = literal_kernel<M, SOP, END>;
   const int grid = n < 65535 ? n : 65535;
   return launch_with_lds((const void *)kfn, g.lds, [&] {
            hipLaunchKernelGGL(kfn, dim3(grid), dim3(64 * LIT_NW), g.lds, stream, d_seqs, d_offsets, n, g.P, g.R,
@@ -602,6 +675,45 @@ int literal_launch_batch(const uint8_t *d_seqs, const int64_t *d_offsets, int32_
                : launch_lit<4, false>(d_seqs, d_offsets, n, max_lb, g, d_scores, d_final7, d_ws, ca, stream);
   return sop ? launch_lit<2, true>(d_seqs, d_offsets, n, max_lb, g, d_scores, d_final7, d_ws, ca, stream)
              : launch_lit<2, false>(d_seqs, d_offsets, n, max_lb, g, d_scores, d_final7, d_ws, ca, stream);
+}
+
+// ---------------------------------------------------------------------------
+// The end search in the literal arithmetic (tsa_score_batch_ends_ex, face and
+// any): always the literal helix, one triple per workgroup, for any parameter
+// set. Only M = 1 and M = 2 are instantiated: with the fold M = 4 (208 VGPRs
+// without it) does not fit 256 VGPRs and would spill to scratch. So a request
+// is admitted where the literal helix has a shape and LC <= 256: LA <= 4095,
+// LB <= 4096 (the key's fields, lit_end_fold, hold all of these) and the LDS.
+// TSA_ERANGE otherwise.
+constexpr int32_t LIT_ENDS_MAX_LC = 256;
+int literal_ends_admit(int32_t max_la, int32_t max_lb, int32_t max_lc) {
+  return max_lc <= LIT_ENDS_MAX_LC && literal_shape_ok(max_la, max_lb, max_lc) ? TSA_OK : TSA_ERANGE;
+}
+size_t literal_ends_workspace_bytes(int32_t n, int32_t max_la, int32_t max_lb, int32_t max_lc) {
+  return literal_workspace_bytes(n, max_la, max_lb, max_lc);
+}
+void literal_describe_ends(int32_t max_la, int32_t max_lb, int32_t max_lc, bool face, char *buf, size_t len) {
+  const LitGeom g = lit_geom(max_la, max_lb, max_lc);
+  snprintf(buf, len, "plane literal-helix M=%d P=%d ends=%s", g.M, g.P, face ? "face" : "any");
+}
+int literal_launch_ends(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, int32_t max_la,
+                        int32_t max_lb, int32_t max_lc, const KParams &kp, bool face, int32_t *d_scores,
+                        int32_t *d_ends, void *d_ws, size_t ws_bytes, hipStream_t stream) {
+  if (n <= 0) return TSA_OK;
+  if (!d_ends) return TSA_EINVAL;
+  const int rc = literal_ends_admit(max_la, max_lb, max_lc);
+  if (rc) return rc;
+  if (n > 65535) return TSA_EINVAL;  // the callers chunk
+  if (ws_bytes < literal_ends_workspace_bytes(n, max_la, max_lb, max_lc)) return TSA_ENOMEM;
+  const LitGeom g = lit_geom(max_la, max_lb, max_lc);
+  LitArgs ca = lit_args(kp);
+  ca.end_face = face ? 1 : 0;
+  const bool sop = kp.s3_mode == TSA_S3_SOP;
+  if (g.M == 1)
+    return sop ? launch_lit<1, true, true>(d_seqs, d_offsets, n, max_lb, g, d_scores, d_ends, d_ws, ca, stream)
+               : launch_lit<1, false, true>(d_seqs, d_offsets, n, max_lb, g, d_scores, d_ends, d_ws, ca, stream);
+  return sop ? launch_lit<2, true, true>(d_seqs, d_offsets, n, max_lb, g, d_scores, d_ends, d_ws, ca, stream)
+             : launch_lit<2, false, true>(d_seqs, d_offsets, n, max_lb, g, d_scores, d_ends, d_ws, ca, stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -97,6 +97,7 @@ struct LitArgs {
   // its pair score a match (1) or not (0), to M by the successor's indicators
   uint32_t fS[3], fP[2], fM[8];
   int32_t sh, packed;
+  int32_t end_face;         // end search (literal_kernel END): candidates on the end faces only
 };
 LitArgs lit_args(const KParams &kp);
 
@@ -580,6 +581,71 @@ __device__ __forceinline__ uint64_t umax64(uint64_t a, uint64_t b) { return a > 
 __device__ __forceinline__ uint64_t end_key64(uint32_t key, uint32_t w, int NW, uint32_t k) {
   const uint32_t y = (END_LAPMASK - (key & END_LAPMASK)) * (uint32_t)NW + w + 1u, z = k + 1u;
   return ((uint64_t)(key >> END_LAPBITS) << 32) | ((0xFFFFu - y) << 16) | (0xFFFFu - z);
+}
+
+// End search of the literal helix (literal_kernel END). A half
+// holds a full 16-bit word (score_bits up to 16), x - 1 <= 4094 and the lap up
+// to 511 (literal_shape_ok), 37 bits in all, so a position keeps two registers
+// per half: the key
+//   [31:16] half ^ 0x8000   [15:0] 4095 - (x - 1)
+// (the shifted int16 half orders as the wrapped word does, the flipped sign bit
+// makes that the unsigned order) and the lap of the key's last update. The key
+// is replaced on strictly greater only: a position meets its laps in ascending
+// order, so among equal {score, x} the first one kept is the smallest y. This
+// fold depends on the order of the steps (tools/literal_emu.py replays it). A
+// real cell's key is never 0 (x <= 4095), so 0 is "no candidate yet".
+//
+// Classes as end_class's, with x = x': a position that has wrapped (k < xpos0)
+// is at x = xpos0 - k of row lap0 NW + w + 1, the others at x = xpos0 + P - k
+// of the row NW above. LitEndClass holds, for cells x = xq - k of row `row`
+// (0-based) in lap `lap`:
+//   start, width  real candidates are start <= k < start + width (1 <= x <= la,
+//                 the row started and <= lb; face mode: x = la or y = lb);
+//                 widthz the same for the position z = lc, all on a face
+//   add           4095 - (x - 1) but for k;  lap: the lap itself
+struct LitEndClass {
+  uint32_t start, width, widthz, add, lap;
+};
+__device__ __forceinline__ LitEndClass lit_end_class(int32_t face, int32_t xq, int32_t lap, int32_t row,
+                                                     int32_t la, int32_t lb) {
+  const bool ok = lap >= 0 && row < lb;
+  const int32_t lim = ok ? la : 0;
+  auto to_v = [](uint32_t s) -> uint32_t {  // (end_class: one v_mov per term keeps the chain scalar)
+    uint32_t v;
+    asm("v_mov_b32 %0, %1" : "=v"(v) : "s"(s));
+    return v;
+  };
+  LitEndClass e;
+  e.start = to_v((uint32_t)(xq - lim));
+  e.widthz = to_v((uint32_t)lim);
+  e.width = to_v(face ? (uint32_t)(!ok ? 0 : row + 1 == lb ? la : 1) : (uint32_t)lim);
+  e.add = to_v((uint32_t)(4096 - xq));
+  e.lap = to_v((uint32_t)lap);
+  return e;
+}
+// Fold register `best` (the MAX7 of positions k0 and k0 + 64 M, in its halves)
+// into their keys and laps.
+template <int M, bool FACE>
+__device__ __forceinline__ void lit_end_fold(uint32_t best, uint32_t k0, uint32_t kz, const LitEndClass &eA,
+                                             const LitEndClass &eB, uint32_t (&key)[2], uint32_t (&klap)[2]) {
+  const uint32_t bx = best ^ 0x80008000u;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const uint32_t k = k0 + 64u * M * h;
+    const uint32_t hv = h ? (bx & 0xFFFF0000u) : (bx << 16);
+    const uint32_t wa = FACE ? (k == kz ? eA.widthz : eA.width) : eA.width;
+    const uint32_t wb = FACE ? (k == kz ? eB.widthz : eB.width) : eB.width;
+    const bool inA = k - eA.start < wa, inB = k - eB.start < wb;  // unsigned: start <= k < start + width
+    const uint32_t cand = (inA || inB) ? hv + (inA ? eA.add : eB.add) + k : 0u;
+    const bool up = cand > key[h];
+    key[h] = up ? cand : key[h];
+    klap[h] = up ? (inA ? eA.lap : eB.lap) : klap[h];
+  }
+}
+// A position's key with its lap, wave w and position k: {score : ~(x-1)} : ~y : ~z
+__device__ __forceinline__ uint64_t lit_end_key64(uint32_t key, uint32_t lap, uint32_t w, int NW, uint32_t k) {
+  const uint32_t y = lap * (uint32_t)NW + w + 1u, z = k + 1u;
+  return ((uint64_t)key << 32) | ((0xFFFFu - y) << 16) | (0xFFFFu - z);
 }
 
 // Shift a packed per-position value one position up the helix (k <- k-1).

@@ -1081,3 +1081,208 @@ int tsa_describe_score_ends_plan(int32_t n, int32_t max_la, int32_t max_lb, int3
 }
 
 }  // extern "C"
+
+// ---- end-free scores with a kernel choice (tsa_score_batch_ends_ex) ------------
+namespace {
+
+enum EndsRoute { ENDS_FACTORED = 0, ENDS_LITERAL = 1 };
+
+// The literal end search's admission, host only: any parameter set; with
+// score_bits = 0 the int16 halves must hold the unwrapped range.
+int literal_score_ends_admit(int32_t max_la, int32_t max_lb, int32_t max_lc, const tsa_params *p) {
+  KParams kp;
+  if (build_kparams(p, &kp)) return TSA_EINVAL;
+  if (p->score_bits == 0) {
+    const Range r = value_bound(p, max_la, max_lb, max_lc);
+    if (r.lo < -32768 || r.hi > 32767) return TSA_ERANGE;
+  }
+  return literal_ends_admit(max_la, max_lb, max_lc);
+}
+
+// Which end search a face / any request runs under `kernel` (0..3, checked by
+// the caller), host only: TSA_OK and *route, or the code the call returns.
+int score_ends_route(int32_t kernel, int32_t max_la, int32_t max_lb, int32_t max_lc, const tsa_params *p,
+                     EndsRoute *route) {
+  *route = ENDS_FACTORED;
+  if (kernel == TSA_KERNEL_CHECKED) return TSA_ERANGE;
+  if (kernel == TSA_KERNEL_PENCIL) return score_ends_admit(max_la, max_lb, max_lc, p);
+  char mode[16] = "";
+  const bool set = override_str("pencil_mode", mode, sizeof mode);
+  const bool lit = set && !strcmp(mode, "literal"), helix = set && !strcmp(mode, "helix");
+  if (set && !lit && !(helix && kernel == TSA_KERNEL_AUTO)) return TSA_EINVAL;
+  if (kernel == TSA_KERNEL_AUTO && !lit) {
+    const int rc = score_ends_admit(max_la, max_lb, max_lc, p);
+    if (rc != TSA_ERANGE || helix) return rc;
+  }
+  *route = ENDS_LITERAL;
+  return literal_score_ends_admit(max_la, max_lb, max_lc, p);
+}
+
+// run_host_ends_on_device for the literal end search.
+int run_host_literal_ends_on_device(int device, const uint8_t *seqs, const int64_t *offsets, int32_t n,
+                                    int32_t max_la, int32_t max_lb, int32_t max_lc, const tsa_params *p,
+                                    bool face, int32_t *scores, int32_t *ends) {
+  int rc = TSA_OK;
+  KParams kp;
+  if ((rc = build_kparams(p, &kp))) return rc;
+  const size_t cap = (size_t)8 << 30;
+  const size_t per = literal_ends_workspace_bytes(1, max_la, max_lb, max_lc);
+  const int32_t chunk = (int32_t)std::max<size_t>(1, std::min<size_t>(std::min(n, 65535), cap / per));
+  const size_t ws_bytes = literal_ends_workspace_bytes(chunk, max_la, max_lb, max_lc);
+  const int64_t base = offsets[0], nbytes = offsets[3 * (int64_t)n] - base;
+  uint8_t *d_seqs = nullptr;
+  int64_t *d_off = nullptr;
+  int32_t *d_scores = nullptr, *d_ends = nullptr;
+  void *d_ws = nullptr;
+  std::vector<int64_t> off((size_t)3 * n + 1);
+  hipStream_t s = nullptr;
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  for (size_t k = 0; k < off.size(); ++k) off[k] = offsets[k] - base;
+  if (hipMalloc(&d_seqs, std::max<int64_t>(nbytes, 1)) != hipSuccess ||
+      hipMalloc(&d_off, off.size() * sizeof(int64_t)) != hipSuccess ||
+      hipMalloc(&d_scores, (size_t)n * sizeof(int32_t)) != hipSuccess ||
+      hipMalloc(&d_ends, (size_t)n * 3 * sizeof(int32_t)) != hipSuccess ||
+      hipMalloc(&d_ws, std::max<size_t>(ws_bytes, 16)) != hipSuccess) {
+    rc = TSA_ENOMEM;
+    goto done;
+  }
+  HIPCHK(hipMemcpyAsync(d_seqs, seqs + base, nbytes, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  for (int32_t c0 = 0; c0 < n && rc == TSA_OK; c0 += chunk) {
+    const int32_t cn = std::min(chunk, n - c0);
+    rc = literal_launch_ends(d_seqs, d_off + 3 * (int64_t)c0, cn, max_la, max_lb, max_lc, kp, face, d_scores + c0,
+                             d_ends + 3 * (int64_t)c0, d_ws, ws_bytes, s);
+  }
+  if (rc) goto done;
+  HIPCHK(hipMemcpyAsync(scores, d_scores, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(ends, d_ends, (size_t)n * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+done:
+  if (s) (void)hipStreamSynchronize(s);
+  if (d_seqs) (void)hipFree(d_seqs);
+  if (d_off) (void)hipFree(d_off);
+  if (d_scores) (void)hipFree(d_scores);
+  if (d_ends) (void)hipFree(d_ends);
+  if (d_ws) (void)hipFree(d_ws);
+  if (s) (void)hipStreamDestroy(s);
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tsa_score_batch_ends_ex(const uint8_t *seqs, const int64_t *offsets, int32_t n, const tsa_params *p,
+                            int32_t end_mode, int32_t kernel, int32_t *scores, int32_t *ends, int32_t device) {
+  if (!seqs || !offsets || !scores || !ends || n < 0 || !params_ok(p)) return TSA_EINVAL;
+  if (end_mode < TSA_END_CORNER || end_mode > TSA_END_ANY) return TSA_EINVAL;
+  if (kernel < TSA_KERNEL_AUTO || kernel > TSA_KERNEL_CHECKED) return TSA_EINVAL;
+  if (kernel == TSA_KERNEL_PENCIL) return tsa_score_batch_ends(seqs, offsets, n, p, end_mode, scores, ends, device);
+  int32_t max_la = 0, max_lb = 0, max_lc = 0;
+  for (int32_t i = 0; i < n; ++i) {
+    const int64_t *o = offsets + 3 * (int64_t)i;
+    if (o[1] < o[0] || o[2] < o[1] || o[3] < o[2]) return TSA_EINVAL;
+    const int32_t la = (int32_t)(o[1] - o[0]), lb = (int32_t)(o[2] - o[1]), lc = (int32_t)(o[3] - o[2]);
+    const int rc = tsa_validate(seqs + o[0], la, seqs + o[1], lb, seqs + o[2], lc, p);
+    if (rc) return rc;
+    max_la = std::max(max_la, la);
+    max_lb = std::max(max_lb, lb);
+    max_lc = std::max(max_lc, lc);
+  }
+  if (n == 0) return TSA_OK;
+  if (kernel == TSA_KERNEL_CHECKED) return TSA_ERANGE;
+  if (end_mode == TSA_END_CORNER) {  // the score plan of that kernel; the ends are the lengths
+    const int nd = tsa_device_count();
+    if (nd <= 0 || device < 0 || device >= nd) return TSA_ENODEV;
+    const int rc = run_host_batch_on_device(device, seqs, offsets, 0, n, p, kernel, scores, nullptr);
+    if (rc) return rc;
+    for (int64_t j = 0; j < 3 * (int64_t)n; ++j) ends[j] = (int32_t)(offsets[j + 1] - offsets[j]);
+    return TSA_OK;
+  }
+  EndsRoute route;
+  const int rc = score_ends_route(kernel, max_la, max_lb, max_lc, p, &route);
+  if (rc) return rc;
+  const int nd = tsa_device_count();
+  if (nd <= 0 || device < 0 || device >= nd) return TSA_ENODEV;
+  const bool face = end_mode == TSA_END_FACE;
+  return route == ENDS_LITERAL
+             ? run_host_literal_ends_on_device(device, seqs, offsets, n, max_la, max_lb, max_lc, p, face, scores, ends)
+             : run_host_ends_on_device(device, seqs, offsets, n, max_la, max_lb, max_lc, p, face, scores, ends);
+}
+
+int tsa_score_ends_workspace_size_ex(int32_t n, int32_t max_la, int32_t max_lb, int32_t max_lc,
+                                     const tsa_params *p, int32_t end_mode, int32_t kernel, size_t *bytes) {
+  if (!bytes || n < 0 || max_la < 1 || max_lb < 1 || max_lc < 1 || !params_ok(p)) return TSA_EINVAL;
+  if (end_mode < TSA_END_CORNER || end_mode > TSA_END_ANY) return TSA_EINVAL;
+  if (kernel < TSA_KERNEL_AUTO || kernel > TSA_KERNEL_CHECKED) return TSA_EINVAL;
+  if (kernel == TSA_KERNEL_PENCIL) return tsa_score_ends_workspace_size(n, max_la, max_lb, max_lc, p, end_mode, bytes);
+  if (kernel == TSA_KERNEL_CHECKED) return TSA_ERANGE;
+  if (end_mode == TSA_END_CORNER) return tsa_batch_workspace_size(n, max_la, max_lb, max_lc, p, kernel, bytes);
+  EndsRoute route;
+  const int rc = score_ends_route(kernel, max_la, max_lb, max_lc, p, &route);
+  if (rc) return rc;
+  *bytes = route == ENDS_LITERAL ? literal_ends_workspace_bytes(n, max_la, max_lb, max_lc)
+                                 : pencil_ends_workspace_bytes(n, max_la, max_lc);
+  return TSA_OK;
+}
+
+int tsa_score_batch_ends_async_ex(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, int32_t max_la,
+                                  int32_t max_lb, int32_t max_lc, const tsa_params *p, int32_t end_mode,
+                                  int32_t kernel, int32_t *d_scores, int32_t *d_ends, void *d_workspace,
+                                  size_t workspace_bytes, void *stream) {
+  if (!d_seqs || !d_offsets || !d_scores || !d_ends || !d_workspace || n < 0 || max_la < 1 || max_lb < 1 ||
+      max_lc < 1 || !params_ok(p))
+    return TSA_EINVAL;
+  if (end_mode < TSA_END_CORNER || end_mode > TSA_END_ANY) return TSA_EINVAL;
+  if (kernel < TSA_KERNEL_AUTO || kernel > TSA_KERNEL_CHECKED) return TSA_EINVAL;
+  if (kernel == TSA_KERNEL_PENCIL)
+    return tsa_score_batch_ends_async(d_seqs, d_offsets, n, max_la, max_lb, max_lc, p, end_mode, d_scores, d_ends,
+                                      d_workspace, workspace_bytes, stream);
+  if (kernel == TSA_KERNEL_CHECKED) return TSA_ERANGE;
+  hipStream_t s = (hipStream_t)stream;
+  if (end_mode == TSA_END_CORNER) {
+    const int rc = score_batch_async(d_seqs, d_offsets, n, max_la, max_lb, max_lc, p, kernel, d_scores,
+                                     d_workspace, workspace_bytes, stream, 0);
+    if (rc || n == 0) return rc;
+    hipLaunchKernelGGL(ends_fill_lengths, dim3((n + 255) / 256), dim3(256), 0, s, d_offsets, n, d_ends);
+    return hipGetLastError() == hipSuccess ? TSA_OK : TSA_EDEVICE;
+  }
+  EndsRoute route;
+  int rc = score_ends_route(kernel, max_la, max_lb, max_lc, p, &route);
+  if (rc) return rc;
+  if (route == ENDS_FACTORED)
+    return tsa_score_batch_ends_async(d_seqs, d_offsets, n, max_la, max_lb, max_lc, p, end_mode, d_scores, d_ends,
+                                      d_workspace, workspace_bytes, stream);
+  if (tsa_device_count() <= 0) return TSA_ENODEV;
+  if (workspace_bytes < literal_ends_workspace_bytes(n, max_la, max_lb, max_lc)) return TSA_ENOMEM;
+  KParams kp;
+  if ((rc = build_kparams(p, &kp))) return rc;
+  for (int32_t c0 = 0; c0 < n; c0 += 65535) {
+    const int32_t cn = std::min<int32_t>(65535, n - c0);
+    rc = literal_launch_ends(d_seqs, d_offsets + 3 * (int64_t)c0, cn, max_la, max_lb, max_lc, kp,
+                             end_mode == TSA_END_FACE, d_scores + c0, d_ends + 3 * (int64_t)c0, d_workspace,
+                             workspace_bytes, s);
+    if (rc) return rc;
+  }
+  return TSA_OK;
+}
+
+int tsa_describe_score_ends_plan_ex(int32_t n, int32_t max_la, int32_t max_lb, int32_t max_lc,
+                                    const tsa_params *p, int32_t end_mode, int32_t kernel, char *buf, size_t len) {
+  if (!buf || len == 0 || n < 1 || max_la < 1 || max_lb < 1 || max_lc < 1 || !params_ok(p)) return TSA_EINVAL;
+  if (end_mode < TSA_END_CORNER || end_mode > TSA_END_ANY) return TSA_EINVAL;
+  if (kernel < TSA_KERNEL_AUTO || kernel > TSA_KERNEL_CHECKED) return TSA_EINVAL;
+  if (kernel == TSA_KERNEL_PENCIL)
+    return tsa_describe_score_ends_plan(n, max_la, max_lb, max_lc, p, end_mode, buf, len);
+  if (kernel == TSA_KERNEL_CHECKED) return TSA_ERANGE;
+  if (end_mode == TSA_END_CORNER) return tsa_describe_plan(n, max_la, max_lb, max_lc, p, kernel, 1, buf, len);
+  EndsRoute route;
+  const int rc = score_ends_route(kernel, max_la, max_lb, max_lc, p, &route);
+  if (rc) return rc;
+  if (route == ENDS_FACTORED) return tsa_describe_score_ends_plan(n, max_la, max_lb, max_lc, p, end_mode, buf, len);
+  literal_describe_ends(max_la, max_lb, max_lc, end_mode == TSA_END_FACE, buf, len);
+  return describe_overrides(buf, len);
+}
+
+}  // extern "C"

@@ -118,6 +118,18 @@ size_t literal_workspace_bytes(int32_t n, int32_t max_la, int32_t max_lb, int32_
 int literal_launch_batch(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, int32_t max_la,
                          int32_t max_lb, int32_t max_lc, const KParams &kp, int32_t *d_scores,
                          int32_t *d_final7, void *d_ws, size_t ws_bytes, hipStream_t stream);
+// The end search of the literal helix (tsa_score_batch_ends_ex under face and
+// any, literal_kernel END): d_scores[i] the largest MAX7 over triple i's real
+// cells (face: those with x = la, y = lb or z = lc) in the RTL's wrapped
+// arithmetic, d_ends[3i..3i+2] the cell (smallest x, then y, then z among
+// equals). Any parameter set; TSA_ERANGE outside literal_shape_ok. One launch,
+// n <= 65535; the workspace is the literal ring and may hold anything.
+int literal_ends_admit(int32_t max_la, int32_t max_lb, int32_t max_lc);
+size_t literal_ends_workspace_bytes(int32_t n, int32_t max_la, int32_t max_lb, int32_t max_lc);
+void literal_describe_ends(int32_t max_la, int32_t max_lb, int32_t max_lc, bool face, char *buf, size_t len);
+int literal_launch_ends(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, int32_t max_la,
+                        int32_t max_lb, int32_t max_lc, const KParams &kp, bool face, int32_t *d_scores,
+                        int32_t *d_ends, void *d_ws, size_t ws_bytes, hipStream_t stream);
 // Which literal kernel a batch runs (TSA_KERNEL_PLANE): the literal lap
 // schedule (a few cubes, lap_kernel LIT), the literal helix (batches the
 // helix shape holds) or the plane sweep (the rest; traceback), by a cost

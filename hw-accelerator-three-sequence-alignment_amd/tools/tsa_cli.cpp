@@ -2,7 +2,7 @@
 // "TriAlign Score: <n>" (src/TriAlign_tb.sv:339-341).
 //   tsa A.dat B.dat C.dat [--kernel auto|plane|pencil] [--device N]
 //       [--s3 rtl|sop] [--bits B] [--match M --mismatch X --go O --ge E]
-//       [--states] [--align [--end corner|face|any] [--grid]] [--score-end face|any]
+//       [--states] [--align [--end corner|face|any] [--grid]] [--score-end face|any [--kernel plane|auto]]
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,7 +21,11 @@ static int usage() {
           "                       tsa_align_batch_grid, or tsa_align_batch_grid_ends with --end face|any)\n"
           "           [--score-end face|any]   (without --align: the end-free score and its end cell,\n"
           "                                     tsa_score_batch_ends; no alignment is traced. Its plan is\n"
-          "                                     always the helix: with --kernel or --states a usage error)\n"
+          "                                     the factored helix; --kernel plane runs the end search of the\n"
+          "                                     literal helix instead (any parameter set), --kernel auto the\n"
+          "                                     factored one where it admits the request and the literal one\n"
+          "                                     otherwise (tsa_score_batch_ends_ex). With --kernel pencil or\n"
+          "                                     --states a usage error)\n"
           "A/B/C: dat files (one symbol 0..4 per line) or FASTA (A=0 T=1 C=2 G=3 N=4)\n");
   return 2;
 }
@@ -69,7 +73,7 @@ int main(int argc, char **argv) {
     else return usage();
   }
   if (nf != 3 || ((end != TSA_END_CORNER || grid) && !align)) return usage();
-  if (score_end != TSA_END_CORNER && (align || states || kernel_set)) return usage();
+  if (score_end != TSA_END_CORNER && (align || states || (kernel_set && kernel == TSA_KERNEL_PENCIL))) return usage();
   uint8_t *s[3];
   int64_t n[3];
   for (int k = 0; k < 3; ++k) {
@@ -84,7 +88,9 @@ int main(int argc, char **argv) {
     int32_t en[3] = {0, 0, 0};
     if (seqs)
       for (int k = 0; k < 3; ++k) memcpy(seqs + off[k], s[k], (size_t)n[k]);
-    const int rc = seqs ? tsa_score_batch_ends(seqs, off, 1, &p, score_end, &score, en, device) : TSA_ENOMEM;
+    const int rc = !seqs ? TSA_ENOMEM
+                   : kernel_set ? tsa_score_batch_ends_ex(seqs, off, 1, &p, score_end, kernel, &score, en, device)
+                                : tsa_score_batch_ends(seqs, off, 1, &p, score_end, &score, en, device);
     free(seqs);
     if (rc) { fprintf(stderr, "tsa: %s (%d)\n", tsa_strerror(rc), rc); return 1; }
     printf("TriAlign Score:        \t%d\n", score);

@@ -438,9 +438,9 @@ int tsa_align_batch_grid_ends(const uint8_t *seqs, const int64_t *offsets, int32
  * the helix plan's with " ends=face" or " ends=any" in place of the estimate,
  * and tsa_describe_plan's (synchronous, TSA_KERNEL_AUTO) for the corner.
  *
- * Not covered: the literal helix and the lap kernels (so no end-free score
- * where only the literal arithmetic is exact), cubes with max_lc > 256, and
- * more than one device per call. */
+ * Not covered by these four: the literal helix (tsa_score_batch_ends_ex below
+ * is the end-free score where only the literal arithmetic is exact), the lap
+ * kernels, cubes with max_lc > 256, and more than one device per call. */
 int tsa_score_batch_ends(const uint8_t *seqs, const int64_t *offsets, int32_t n,
                          const tsa_params *p, int32_t end_mode, int32_t *scores,
                          int32_t *ends /* 3n */, int32_t device);
@@ -456,6 +456,66 @@ int tsa_score_batch_ends_async(const uint8_t *d_seqs, const int64_t *d_offsets,
 int tsa_describe_score_ends_plan(int32_t n, int32_t max_la, int32_t max_lb,
                                  int32_t max_lc, const tsa_params *p,
                                  int32_t end_mode, char *buf, size_t len);
+
+/* The same four with a kernel choice, as tsa_score_gpu_ex is to tsa_score_gpu:
+ * the end-free screen in the RTL's literal wrapped arithmetic, so that it
+ * returns tsa_align_batch_ends's score and end cell for every parameter set --
+ * gap_open < gap_extend, cubes whose a-priori bound leaves the f16 range, and
+ * any score_bits, where the words really wrap -- without a pointer cube.
+ *
+ *   TSA_KERNEL_PENCIL   the call above in every respect: codes, plan text,
+ *                       workspace.
+ *   TSA_KERNEL_PLANE    the literal helix end search (literal_kernel END): the
+ *                       literal helix with one triple per workgroup -- never
+ *                       the literal lap, never the plane sweep -- folding the
+ *                       MAX7 of every real cell's seven states as it sweeps.
+ *                       Admitted for any parameter set with max_la <= 4095,
+ *                       max_lb <= 4096 and max_lc <= 256 (and an LDS that
+ *                       holds the tables); TSA_ERANGE otherwise. max_lc <= 256
+ *                       because only the M = 1 and M = 2 kernels exist: with
+ *                       the fold the M = 4 kernel (257..512) does not fit the
+ *                       register file without scratch. score_bits = 0 runs in
+ *                       16-bit words and is TSA_ERANGE where the unwrapped
+ *                       range leaves int16 (as everywhere).
+ *   TSA_KERNEL_AUTO     the factored helix where the call above admits the
+ *                       request, else the literal end search where that admits
+ *                       it, else TSA_ERANGE.
+ *   TSA_KERNEL_CHECKED  TSA_ERANGE (no checked end search).
+ * Anything outside 0..3 is TSA_EINVAL, checked next to end_mode; the rest of
+ * the validation order is the call's above, all before any device work.
+ *
+ * TSA_END_CORNER fills ends with the lengths and runs the score plan of that
+ * kernel (tsa_score_batch_async's on the async call, with
+ * tsa_batch_workspace_size's workspace for that kernel). The literal end
+ * search's workspace is the literal ring of the geometry
+ * (tsa_score_ends_workspace_size_ex; it may hold anything on entry), its plan
+ * text "plane literal-helix M=<m> P=<p> ends=face|any" and the overrides;
+ * tsa_kernel_launch_count rises by one per launch, one launch per chunk of at
+ * most 65535 triples.
+ *
+ * Overrides: under PLANE and AUTO pencil_mode = literal forces the literal end
+ * search; under AUTO pencil_mode = helix forces the factored one (TSA_ERANGE
+ * where it does not admit the request); any other set pencil_mode is
+ * TSA_EINVAL.
+ *
+ * Not covered: an end search on the literal lap or the plane sweep, cubes with
+ * max_lc > 256, and more than one device per call. */
+int tsa_score_batch_ends_ex(const uint8_t *seqs, const int64_t *offsets, int32_t n,
+                            const tsa_params *p, int32_t end_mode, int32_t kernel,
+                            int32_t *scores, int32_t *ends /* 3n */, int32_t device);
+int tsa_score_ends_workspace_size_ex(int32_t n, int32_t max_la, int32_t max_lb,
+                                     int32_t max_lc, const tsa_params *p,
+                                     int32_t end_mode, int32_t kernel, size_t *bytes);
+int tsa_score_batch_ends_async_ex(const uint8_t *d_seqs, const int64_t *d_offsets,
+                                  int32_t n, int32_t max_la, int32_t max_lb,
+                                  int32_t max_lc, const tsa_params *p,
+                                  int32_t end_mode, int32_t kernel, int32_t *d_scores,
+                                  int32_t *d_ends, void *d_workspace,
+                                  size_t workspace_bytes, void *stream);
+int tsa_describe_score_ends_plan_ex(int32_t n, int32_t max_la, int32_t max_lb,
+                                    int32_t max_lc, const tsa_params *p,
+                                    int32_t end_mode, int32_t kernel, char *buf,
+                                    size_t len);
 
 /* Device-resident traceback: tsa_align_batch on sequences that are already in
  * device memory, with results that stay there. d_* are device pointers on the

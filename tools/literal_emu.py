@@ -1,5 +1,6 @@
 """CPU replay of the literal helix (csrc/pencil_kernel.hip, LIT): the RTL's
-literal arithmetic in the helix's schedule.
+literal arithmetic in the helix's schedule, and of its end search
+(emulate_ends: literal_kernel END, the fold in the kernel's order).
 
 TEST/DESIGN INFRASTRUCTURE (tests/test_pencil_schedule.py checks it against
 the oracle). The pull-form recurrence needs all 7 states of 7 predecessors
@@ -43,10 +44,62 @@ def penalties(go, ge):
 
 def emulate(a, b, c, match=1, mismatch=-1, go=2, ge=1, sop=False, bits=12):
     """(score, final7) of one triple by the literal helix schedule."""
+    return _sweep(a, b, c, match, mismatch, go, ge, sop, bits, None, None)
+
+
+# ---- the end search (literal_kernel END; csrc/pencil_common.h lit_end_fold) ----
+# A position keeps, per half, the key {half ^ 0x8000 : 4095 - (x - 1)} and the
+# lap of the key's last update; the key is replaced on strictly greater only,
+# so the fold depends on the order of the steps, which _sweep replays.
+
+def end_key(half, x):
+    """The 32-bit key of a real cell: `half` the 16-bit shifted word, 1 <= x <= 4095."""
+    return (((half & 0xFFFF) ^ 0x8000) << 16) | (4095 - (x - 1))
+
+
+def end_key64(key, lap, w, k):
+    """A position's key with its lap, wave and position: {score : ~(x-1)} : ~y : ~z."""
+    y, z = lap * NW + w + 1, k + 1
+    return (key << 32) | ((0xFFFF - y) << 16) | (0xFFFF - z)
+
+
+def end_decode(key64, sh):
+    """(score, (x, y, z)) of a reduced key; sh = 16 - SCORE_BITS."""
+    top = key64 >> 32
+    half = (top >> 16) ^ 0x8000
+    score = (half - 0x10000 if half & 0x8000 else half) >> sh
+    return score, (4095 - (top & 0xFFFF) + 1, 0xFFFF - ((key64 >> 16) & 0xFFFF), 0xFFFF - (key64 & 0xFFFF))
+
+
+def emulate_ends(triples_or_one, end=("any", "face"), max_lens=None, match=1, mismatch=-1, go=2, ge=1, sop=False,
+                 bits=12):
+    """The end search of the literal helix, replayed: for one triple (a, b, c)
+    a dict {mode: (score, (x1, y1, z1))} over the modes in `end` (a single
+    mode gives its pair alone); for a list of triples a list of those, all in
+    the geometry of the batch's maxima. max_lens = (max_la, max_lb, max_lc)
+    gives that geometry explicitly (a short triple in a larger batch)."""
+    one = len(triples_or_one) == 3 and np.ndim(triples_or_one[0]) == 1
+    triples = [triples_or_one] if one else list(triples_or_one)
+    modes = (end,) if isinstance(end, str) else tuple(end)
+    if max_lens is None:
+        max_lens = tuple(max(len(t[j]) for t in triples) for j in range(3))
+    out = []
+    for a, b, c in triples:
+        r = _sweep(a, b, c, match, mismatch, go, ge, sop, bits, max_lens, modes)
+        out.append(r[modes[0]] if isinstance(end, str) else r)
+    return out[0] if one else out
+
+
+def _sweep(a, b, c, match, mismatch, go, ge, sop, bits, max_lens, ends):
+    """The schedule. ends = None: (score, final7) at the corner. ends = a tuple
+    of modes: the end search's {mode: (score, end)}; the geometry (M, P) is
+    that of max_lens, the steps and the real cells the triple's own."""
     la, lb, lc = len(a), len(b), len(c)
-    M = 1 if lc <= 128 else 2 if lc <= 256 else 4
+    gla, glb, glc = max_lens if max_lens is not None else (la, lb, lc)
+    assert la <= gla and lb <= glb and lc <= glc
+    M = 1 if glc <= 128 else 2 if glc <= 256 else 4
     KS = 128 * M
-    P = max(la + 1, KS)
+    P = max(gla + 1, KS)
     P = -(-P // M) * M
     if M <= 2:  # the kernel's TSA_LIT_STATIC: P a multiple of 4
         P = -(-P // 4) * 4
@@ -116,6 +169,35 @@ def emulate(a, b, c, match=1, mismatch=-1, go=2, ge=1, sop=False, bits=12):
     lap_f, w_f, k_f = (lb - 1) // NW, (lb - 1) % NW, lc - 1
     t_f = lap_f * P + la + S * w_f + k_f          # x' = la at u = la
     fin = None
+    sh = 16 - (bits or 16)
+    if ends is not None:  # per mode: key and lap of every wave's positions
+        ekey = {m: np.zeros((NW,) + shape, np.int64) for m in ends}
+        elap = {m: np.zeros((NW,) + shape, np.int64) for m in ends}
+    # the kernel runs whole groups of four steps: the cells past t_f are computed
+    # too (and folded, were they not masked)
+    t_end = t_f + 1 if ends is None else -(-(t_f + 1) // 4) * 4
+
+    def fold(w, d, Sst):
+        """lit_end_fold for wave w at this step: class A (wrapped) x = xpos0 - k
+        of row lap0 NW + w, class B x = xpos0 + P - k of the row NW above."""
+        best = np.maximum.reduce(Sst)
+        hv = (((best << sh) & 0xFFFF) ^ 0x8000) << 16
+        for m in ends:
+            cand = np.zeros(shape, np.int64)
+            clap = np.zeros(shape, np.int64)
+            for xq, lap in ((d["xpos0"] + P, d["lap0"] - 1), (d["xpos0"], d["lap0"])):  # B, then A wins
+                row = lap * NW + w
+                ok = lap >= 0 and row < lb
+                lim = la if ok else 0
+                start = (xq - lim) & 0xFFFFFFFF
+                width = lim if m == "any" else (0 if not ok else la if row + 1 == lb else 1)
+                wd = np.where(kpos == lc - 1, lim, width) if m == "face" else np.full(shape, width)
+                inc = ((kpos - start) & 0xFFFFFFFF) < wd
+                cand = np.where(inc, (hv + (4096 - xq) + kpos) & 0xFFFFFFFF, cand)
+                clap = np.where(inc, lap, clap)
+            up = cand > ekey[m][w]
+            ekey[m][w] = np.where(up, cand, ekey[m][w])
+            elap[m][w] = np.where(up, clap, elap[m][w])
 
     def shift(v, face):
         out = np.empty_like(v)
@@ -125,7 +207,7 @@ def emulate(a, b, c, match=1, mismatch=-1, go=2, ge=1, sop=False, bits=12):
         out[0, 0, 1] = v[M - 1, 63, 0]
         return out
 
-    for t in range(t_f + 1):
+    for t in range(t_end):
         PH = t & 1
         outs = [None] * NW
         for w in range(NW):
@@ -143,6 +225,8 @@ def emulate(a, b, c, match=1, mismatch=-1, go=2, ge=1, sop=False, bits=12):
                 row = d["lap0"] * NW + w                # 0-based row of this lap
                 d["bn"] = np.where(inj, int(code(b, np.array(row + 1))), d["bn"])
             Sst = [MM, X, Y, Z, XY, YZ, XZ]
+            if ends is not None:
+                fold(w, d, Sst)
             if t == t_f and w == w_f:
                 pos = tuple(np.argwhere(kpos == k_f)[0])
                 fin = [int(v[pos]) for v in Sst]
@@ -174,4 +258,16 @@ def emulate(a, b, c, match=1, mismatch=-1, go=2, ge=1, sop=False, bits=12):
         for w in range(NW):
             xr[w, t & 3] = outs[w]
         ring[t % R] = outs[NW - 1]
-    return max(fin), fin
+    if ends is None:
+        return max(fin), fin
+    res = {}
+    for m in ends:  # per wave over its positions k < lc, then across the waves
+        bk = 0
+        for w in range(NW):
+            wk = 0
+            for idx in np.argwhere((kpos < lc) & (ekey[m][w] != 0)):
+                idx = tuple(idx)
+                wk = max(wk, end_key64(int(ekey[m][w][idx]), int(elap[m][w][idx]), w, int(kpos[idx])))
+            bk = max(bk, wk)
+        res[m] = end_decode(bk, sh)
+    return res

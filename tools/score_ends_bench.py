@@ -10,6 +10,11 @@ leg that are not timed; the figure is the train's time over its length. The
 cost of the end search is read against the corner leg of the same pass.
   python tools/score_ends_bench.py --n 512 --L 256
   python tools/score_ends_bench.py --n 512 --L 64 --out profiles/score_ends.jsonl
+  python tools/score_ends_bench.py --kernel plane --n 512 --L 256 --out profiles/score_ends_literal.jsonl
+--kernel plane times the literal arithmetic instead: the corner leg is the
+literal helix score (tsa_score_batch_async, TSA_KERNEL_PLANE under
+pencil_mode=literal), the face and any legs its end search
+(tsa_score_batch_ends_async_ex, TSA_KERNEL_PLANE).
 Prints one JSON line per process (every pass's figures, and per leg the median,
 min and max in ms) and appends it to --out when given. The first call of each
 leg is also a check: the corner leg equals tsa_score_batch_ends' corner mode,
@@ -31,10 +36,16 @@ def main():
     ap.add_argument("--passes", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--train", type=int, default=20)
+    ap.add_argument("--kernel", choices=("pencil", "plane"), default="pencil",
+                    help="pencil: the factored helix (default); plane: the literal helix and its end search")
     ap.add_argument("--out", default=None, help="append the JSON line to this file")
     args = ap.parse_args()
     import bench
     tsa = bench.load_pkg()
+    kernel = args.kernel
+    ends_kernel = None if kernel == "pencil" else kernel      # None: the entry points without a kernel argument
+    if kernel == "plane":
+        tsa.set_override("pencil_mode", "literal")            # the literal helix for every leg, whatever the cost model
     import torch
     import tsa_amd.synth as synth
     n, L = args.n, args.L
@@ -50,24 +61,25 @@ def main():
         legs[name] = queue_of(sc, en, ws, ws_bytes)
         outs[name] = (sc, en, ws)
 
-    add("corner", tsa.workspace_size(n, L, L, L, kernel="pencil"),
+    add("corner", tsa.workspace_size(n, L, L, L, kernel=kernel),
         lambda sc, en, ws, nb: lambda: tsa.score_batch_async(d_seqs.data_ptr(), d_offs.data_ptr(), n, L, L, L,
-                                                             sc.data_ptr(), ws.data_ptr(), nb, stream, kernel="pencil"))
+                                                             sc.data_ptr(), ws.data_ptr(), nb, stream, kernel=kernel))
     for mode in ("face", "any"):
-        add(mode, tsa.score_ends_workspace_size(n, L, L, L, end=mode),
+        add(mode, tsa.score_ends_workspace_size(n, L, L, L, end=mode, kernel=ends_kernel),
             lambda sc, en, ws, nb, mode=mode: lambda: tsa.score_batch_ends_async(
                 d_seqs.data_ptr(), d_offs.data_ptr(), n, L, L, L, sc.data_ptr(), en.data_ptr(), ws.data_ptr(), nb,
-                stream, end=mode))
-    plans = {"corner": tsa.describe_plan(n, L, L, L, kernel="pencil", sync=False),
-             "face": tsa.describe_score_ends_plan(n, L, L, L, end="face"),
-             "any": tsa.describe_score_ends_plan(n, L, L, L, end="any")}
+                stream, end=mode, kernel=ends_kernel))
+    plans = {"corner": tsa.describe_plan(n, L, L, L, kernel=kernel, sync=False),
+             "face": tsa.describe_score_ends_plan(n, L, L, L, end="face", kernel=ends_kernel),
+             "any": tsa.describe_score_ends_plan(n, L, L, L, end="any", kernel=ends_kernel)}
     for q in legs.values():          # first call: the check
         q()
     torch.cuda.synchronize()
     h = {k: outs[k][0].cpu().numpy() for k in legs}
     ok = bool((h["any"] >= h["face"]).all() and (h["face"] >= h["corner"]).all())
     k = min(n, 64)                   # the corner against the synchronous entry point, on a part of the batch
-    ref = tsa.score_batch_ends(seqs=seqs[:int(offs[3 * k])], offsets=offs[:3 * k + 1], end="corner")
+    ref = tsa.score_batch_ends(seqs=seqs[:int(offs[3 * k])], offsets=offs[:3 * k + 1], end="corner",
+                               kernel=ends_kernel)
     ok = ok and [s for s, _ in ref] == h["corner"][:k].tolist()
     for _ in range(args.warmup):
         for q in legs.values():
@@ -85,7 +97,7 @@ def main():
             t1.synchronize()
             row[name] = round(t0.elapsed_time(t1) / args.train, 4)
         passes.append(row)
-    res = {"bench": "score_ends", "n": n, "shape": [L, L, L], "train": args.train, "warmup": args.warmup,
+    res = {"bench": "score_ends", "kernel": kernel, "n": n, "shape": [L, L, L], "train": args.train, "warmup": args.warmup,
            "passes": passes, "plans": plans, "legs_consistent": ok, "version": tsa.version(), "pid": os.getpid()}
     for name in legs:
         ts = [p[name] for p in passes]
