@@ -32,7 +32,7 @@
 namespace tsa {
 
 constexpr int LIT_NW = 8, LIT_S = 2, LIT_RING_EXTRA = 8;
-// M <= 2: P a multiple of 4, so (as in the pencil helix, TSA_EV_STATIC) each
+// M <= 2: P a multiple of 4, so (as in the pencil helix, EV_SKIP) each
 // wave meets the x' = 0 half-mask and lap-wrap events at one static step of
 // its four-step group, the x' = 0 register is the step's parity (M = 2), and
 // the injection is a tracked mask with no per-step branch

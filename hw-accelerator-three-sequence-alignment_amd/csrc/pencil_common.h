@@ -1,4 +1,4 @@
-// pencil_common.h -- device helpers, packed constants and build knobs shared
+// pencil_common.h -- device helpers and packed constants shared
 // by the register-systolic kernels: the batch helix (pencil_kernel.hip) and the
 // single-cube lap kernel (lap_kernel.hip). See pencil_kernel.hip for the design.
 #pragma once
@@ -17,46 +17,6 @@ typedef short s16x2 __attribute__((ext_vector_type(2)));
 
 constexpr size_t LDS_MAX = 160 * 1024;
 constexpr int REC_BYTES = 16;      // {Iy, Ixy, Iyz, best} packed pairs per lane
-#ifndef TSA_A_B64  // V-space M = 2: a step's A codes as one ds_read_b64 (pencil_kernel)
-#define TSA_A_B64 1
-#endif
-#ifndef TSA_A_PREFETCH  // read the next step's A codes before the step barrier
-#define TSA_A_PREFETCH 1
-#endif
-// A/B knobs of the f16 cell (build-time; see scripts/build_variant.sh)
-#ifndef TSA_DMC        // a&c match term through a per-position scaled delta (no min)
-#define TSA_DMC 1
-#endif
-#ifndef TSA_VMAX3_ASM  // message maxes as explicit v_pk_maximum3_f16 (measured slower:
-#define TSA_VMAX3_ASM 0   // the asm blocks constrain the scheduler more than they save)
-#endif
-#ifndef TSA_GROUPS     // widened GO+GE groups sharing max(Ix,Iy,Iz)
-#define TSA_GROUPS 1
-#endif
-#ifndef TSA_LANE_MASK  // x = 1 lane mask from a scalar shift (one v_cndmask)
-#define TSA_LANE_MASK 1
-#endif
-#ifndef TSA_ROW_NEXT   // next row's per-row terms precomputed once per lap
-#define TSA_ROW_NEXT 1
-#endif
-#ifndef TSA_PIN_ROW    // pin the per-row registers after the x = 1 block
-#define TSA_PIN_ROW 1
-#endif
-#ifndef TSA_UNROLL4  // helix loop body of four steps instead of two (M <= 2)
-#define TSA_UNROLL4 1
-#endif
-#ifndef TSA_HM_TRACK  // half mask kept in a register, switched at two events per lap
-#define TSA_HM_TRACK 1
-#endif
-#ifndef TSA_SETPRIO  // helix: priority 0 for the cell arithmetic, 1 for the tail
-#define TSA_SETPRIO 1
-#endif
-#ifndef TSA_IS_STATIC  // M = 2: the x = 1 register index from the wave parity
-#define TSA_IS_STATIC 1
-#endif
-#ifndef TSA_SCHED_FENCE  // sched_barrier fences around the helix cell arithmetic
-#define TSA_SCHED_FENCE 1
-#endif
 
 // Packed (both halves) constants. int16 form: two's complement; exact-f16 form
 // (helix kernel, F16): f16 bits, pair penalties and f_pair with the mismatch
@@ -285,17 +245,10 @@ __device__ __forceinline__ h2 H(uint32_t v) { return __builtin_bit_cast(h2, v); 
 __device__ __forceinline__ uint32_t U(h2 v) { return __builtin_bit_cast(uint32_t, v); }
 __device__ __forceinline__ h2 hmax(h2 a, h2 b) { return __builtin_elementwise_maximum(a, b); }
 __device__ __forceinline__ h2 hmax3(h2 a, h2 b, h2 c) { return hmax(hmax(a, b), c); }
-// One v_pk_maximum3_f16 exactly: left to itself the compiler CSEs the shared
-// two-input maxes of the message groups and then cannot fuse them into max3s.
-__device__ __forceinline__ h2 vmax3(h2 a, h2 b, h2 c) {
-#if TSA_VMAX3_ASM
-  h2 r;
-  asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-#else
-  return hmax3(a, b, c);
-#endif
-}
+// The messages' maxes: the compiler fuses each into one v_pk_maximum3_f16 where
+// the callers keep the inner pairs distinct (the instruction written as asm
+// measured slower: the asm blocks constrain the scheduler more than they save)
+__device__ __forceinline__ h2 vmax3(h2 a, h2 b, h2 c) { return hmax3(a, b, c); }
 __device__ __forceinline__ h2 hfma(h2 a, h2 b, h2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ uint32_t umin2(uint32_t a, uint32_t b) {
   return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(us2, a),
@@ -336,13 +289,8 @@ __device__ __forceinline__ void cell_messages_f16(
   for (int i = 0; i < M; ++i) {
     // a & c is c's code (a power of two) on a match, 0 otherwise, and
     // DMC = (match - mismatch) / code(c) per position: the product is exact
-#if TSA_DMC
     const h2 eab = H(umin2(a[i] & b[i], Q)), eac = H(a[i] & c[i]);
     const h2 DMCi = H(DMC[i]);
-#else
-    const h2 eab = H(umin2(a[i] & b[i], Q)), eac = H(umin2(a[i] & c[i], Q));
-    const h2 DMCi = DM;
-#endif
     const h2 sXY = hfma(eab, DM, H(inIxy[i]));  // src/PE_1cyc.v:159-161 (+mismatch folded)
     const h2 sXZ = hfma(eac, DMCi, H(inIxz[i]));
     const h2 sYZ = H(inIyz[i]) + H(SBC[i]);
@@ -356,7 +304,6 @@ __device__ __forceinline__ void cell_messages_f16(
     // own state, so the three share max(Ix,Iy,Iz); each target's highest
     // group ({M,Iyz} at 2GO for Ix, {M,Iz,Iyz,Ixz} at GO for Ixy, ...) takes in
     // all 7, so it is MAX7 - penalty, shared by all six gap targets.
-#if TSA_GROUPS
     // vmax3(a, b, c) = max(max(a, b), c): the inner pairs are all distinct, so
     // the compiler cannot CSE one and fuses every pair into one max3
     const h2 S3 = vmax3(sX, sY, sZ);
@@ -367,12 +314,6 @@ __device__ __forceinline__ void cell_messages_f16(
     const h2 C2 = vmax3(sY, sYZ, sZ);
     const h2 C3 = vmax3(sZ, sXZ, sX);
     const h2 best = vmax3(A1, sYZ, sM);  // A1 | Iyz = the six gap states
-#else
-    const h2 pYZ = hmax(sY, sZ), pXZ = hmax(sX, sZ), pXY = hmax(sX, sY);
-    const h2 A1 = hmax3(pYZ, sXY, sXZ), A2 = hmax3(pXZ, sXY, sYZ), A3 = hmax3(pXY, sYZ, sXZ);
-    const h2 C1 = hmax(pXY, sXY), C2 = hmax(pYZ, sYZ), C3 = hmax(pXZ, sXZ);
-    const h2 best = hmax3(A1, A2, sM);
-#endif
     const h2 bO = best - O, bO2 = best - O2;
     oBest[i] = U(best);
     nIx[i] = U(vmax3(sX - E2, A1 - OE, bO2));
@@ -708,18 +649,6 @@ __device__ __forceinline__ void load_a_pair(uint32_t va, uint32_t va_s, uint32_t
   const uint64_t v = *(const __attribute__((address_space(3))) uint64_t *)(uintptr_t)addr;
   a[1] = (uint32_t)v;
   a[0] = (uint32_t)(v >> 32);
-}
-// bfi mask selecting one half (hs) of one lane (ls): the lane bit comes from a
-// scalar shift, so this is one VALU op (v_cndmask with an SGPR-pair mask);
-// the two asm strings differ so the compiler does not merge them into one
-// with a VALU-selected operand.
-__device__ __forceinline__ uint32_t lane_half_mask(int32_t ls, int32_t hs, uint32_t hmLo,
-                                                   uint32_t hmHi) {
-  const uint64_t lm = 1ull << ls;
-  uint32_t m;
-  if (hs) asm("v_cndmask_b32_e64 %0, 0, %1, %2 ; hi" : "=v"(m) : "v"(hmHi), "s"(lm));
-  else asm("v_cndmask_b32_e64 %0, 0, %1, %2 ; lo" : "=v"(m) : "v"(hmLo), "s"(lm));
-  return m;
 }
 // Position k -> (lane, register, half) of the layout above.
 template <int M>

@@ -33,217 +33,88 @@
 //
 // Supported shapes: LC <= 128*M (M = 1 or 2), LA <= 4096, LB <= 4096.
 
+
+// The step (the `step` lambda of pencil_kernel), in the order it executes. One
+// form of each part exists; where the forms differ between instantiations the
+// condition is a shape (the constexpr names RP, FIRSTLAP, A_EVEN, A_B64,
+// MASK_PAIRS, HSK), never a build choice. What each form replaced, and the
+// forms that were built, measured and taken out again, are in DESIGN.md 4.2, 8
+// and Appendix H.
+//
+//  1. A codes. V-space: from registers an even step filled for itself's two
+//     successors (for M = 2 as one ds_read_b64 each, from the table or its copy
+//     shifted by one entry), so no LDS read is pending at an odd step's barrier.
+//     Other forms: read by the step before, ahead of its barrier.
+//  2. Record of the wave above. RP (V-space M = 2, one triple, skew 2): {Iy,
+//     Ixy} from the lane's own record, {Iyz, best} from position k - 1's, by the
+//     address of the read (read_prev); other forms read their own record and
+//     shift it in step 7. Wave 0 reads the ring rows prefetched into xr0; in
+//     V-space it builds the face records of its steps before t_sw from its own
+//     H registers instead (ROLE 3), and the prologue fills only the ring rows
+//     of steps [t_sw, lag).
+//  3. x = 1 injection into the inputs: the half mask of the x = 1 position is
+//     kept in a register and switched at two events per lap (hm_of / ev_of); the
+//     lane's bfi mask is one v_cndmask, shared by a pair of steps
+//     (MASK_PAIRS). The position takes the x = 0 faces, the row's B code (RP:
+//     from the SGPR it lives in) and the per-row terms computed once per lap
+//     (row_terms).
+//  4. The cell: cell_messages{,_f16,_vs,_vi} at priority 0 between two
+//     scheduling fences; the rest of the step runs at priority 1.
+//  5. Final-cell capture, then the record send: one ds_write_b128 per register
+//     to the wave below; the last wave stores to the ring row instead (RP: the
+//     row's uniform base plus the lane's 32-bit offset, the store's saddr form)
+//     and keeps at most STORE_SLACK steps of stores in flight.
+//  6. END: the end search's fold of the step's real cells.
+//  7. Advance: V-space sets H(t + 2); position 0 moves on, its half-mask and
+//     lap-wrap events tested only at the one step of a four-step group where
+//     they can fall (EV_SKIP; V-space M = 2, where P is a multiple of 4); the
+//     own messages shift by DPP wave_ror:1 + v_perm (zshift), the row-above ones
+//     likewise or, RP, by lane 0's v_perm alone (zfix).
+//  8. V-space, even steps: the A reads of step 1.
+//  9. Ring fetch. The RP forms: waves 1 and 2 issue wave 0's rows with
+//     dma16x2_saddr at the even steps of their groups from group t_iss on, the
+//     row of step t + 6 (wave 1) or t + 7 (wave 2), and wait with a counted
+//     vmcnt at the odd steps until only their two newest rows are in flight;
+//     the step barrier is the only synchronisation, and nothing is primed.
+//     Other forms: wave 0 fetches its own row of step t + PD (prime() fills the
+//     pipeline), for non-V-space M = 2 also through dma16x2_saddr.
+// 10. s_waitcnt lgkmcnt(0) + s_barrier: every step at skew 1, every second
+//     step at skew 2 (a wave reads records two steps old).
+
 #include <vector>
 
 #include "pencil_common.h"
-#include "h_table.h"
 #include "lap_kernel.h"
 
 namespace tsa {
 
 
 // waves (= DP rows) per lap: 8, two workgroups per CU, so one computes while
-// the other waits at its barrier. -DTSA_PENCIL_NW=16 (M = 2, f16 rtl only):
-// one 1024-thread workgroup per CU, half the ring traffic -- parity-green and
-// 3 % slower (round 6, profiles/r6j_helix_nw16_ab.jsonl; round 1 likewise)
-#ifndef TSA_PENCIL_NW
-#define TSA_PENCIL_NW 8
-#endif
-constexpr int PENCIL_NW = TSA_PENCIL_NW;
-#ifndef TSA_STORE_SLACK
-#define TSA_STORE_SLACK 4
-#endif
-constexpr int STORE_SLACK = TSA_STORE_SLACK;  // last wave keeps <= this many steps of stores in flight
+// the other waits at its barrier (16 waves, one workgroup per CU and half the
+// ring traffic, measured 3 % slower: profiles/r6j_helix_nw16_ab.jsonl)
+constexpr int PENCIL_NW = 8;
+// the last wave keeps <= this many steps of ring stores in flight (a deeper
+// slack, 8 or 16, measured neutral: DESIGN.md 4.2, "The ring's share")
+constexpr int STORE_SLACK = 4;
 constexpr int MAX_LA = 4096, MAX_LB = 4096, MAX_LC = 1024;
 // LDS-DMA prefetch distance (steps) of wave 0: helix (ring) and lap (hand-off);
 // shorter for wide positions (M pairs per lane) so the record slots fit in LDS
 __host__ __device__ constexpr int helix_pd(int M) { return M >= 8 ? 2 : M >= 4 ? 4 : 8; }
-#ifndef TSA_SKEW  // helix: steps between waves; 2 = one barrier per two steps
-#define TSA_SKEW 2
-#endif
-// skew and record slots per wave; M >= 4 keeps skew 1 (twice the slots would not fit LDS)
-__host__ __device__ constexpr int helix_skew(int M) { return M <= 2 ? TSA_SKEW : 1; }
+// steps between waves, and record slots per wave: 2 up to M = 2, one barrier per
+// two steps (1403-1465 -> 1476-1514 GCUPS over skew 1); M >= 4
+// keeps skew 1 (twice the slots would not fit LDS)
+__host__ __device__ constexpr int helix_skew(int M) { return M <= 2 ? 2 : 1; }
 constexpr int RING_EXTRA = 8;
-// V-space M = 2: the lap period P is a multiple of 4, so each wave meets its
-// half-mask / lap-wrap events (xpos0 = 64M, 128M, P) at one static step of the
-// four-step group (xpos0 is -2w mod 4 at the group start); the other three
-// steps advance with no compare and no branch
-#ifndef TSA_EV_STATIC
-#define TSA_EV_STATIC 1
-#endif
-// V-space M = 2: the face values H(s) = lam q live in SGPRs, read from a
-// constant table of f16 bits (h_table.h) by scalar loads: no VALU add per
-// step, and the bfi / perm that inject them read the SGPR directly. A wave
-// keeps the integer lam q; each four-step group fetches the next group's four
-// values (one four-dword load for lam = 1, where they are contiguous, else one
-// load per value) at the top of its third step, and the fourth step's
-// `s_waitcnt lgkmcnt(0)` before the barrier covers them. At a lap wrap the
-// restarted values come from the same table, waited for in place (once per
-// lap). 0: one v_pk_add_f16 per step on VGPR copies. Parity-green, 8 VALU per
-// group fewer (266 -> 260 with it alone) and measured SLOWER, so off: 1872-1902
-// against 1907-1921 GCUPS, four interleaved bench passes on one box
-// (profiles/r8_helix_ab.jsonl) -- with a scalar load in flight every LDS wait
-// of the step that issues it is an lgkmcnt(0). (An earlier SGPR form encoded
-// each value in SALU, 11 instructions per step, and measured slower too:
-// 1667 / 1645 vs 1697 / 1687 GCUPS, profiles/r5b_helix_ab.jsonl.)
-#ifndef TSA_H_TAB
-#define TSA_H_TAB 0
-#endif
-// V-space: step s's x = 1 injection applied to the state registers at the end
-// of step s - 1 (before the step barrier), not to the inputs at the start of
-// step s, where it stood between the barrier and the cell
-#ifndef TSA_PREINJ  // (measured neutral with the SALU-encoded H: 1646 / 1646 vs 1667 / 1645, r5b)
-#define TSA_PREINJ 0
-#endif
-// V-space M = 2: a reader takes {Iyz, best} of the row above from the record of
-// position k - 1 -- register i - 1 of its own lane, or register M - 1 of lane
-// - 1 (lane 63 for lane 0) for register 0 -- by the address of its LDS read,
-// not from its own record through a DPP wave_ror:1. Lane 0's v_perm stays (the
-// z = 0 face in the low half, lane 63's low half in the high half); no record
-// write, ring store or ring fill changes. 0: own record, DPP + v_perm. 8 VALU
-// per group fewer (266 -> 258); 1932-1951 against 1907-1921 GCUPS, every pass
-// above every pass of the parent (profiles/r8_helix_ab.jsonl)
-#ifndef TSA_REC_PREV
-#define TSA_REC_PREV 1
-#endif
-// (The last wave's ring records as buffer stores -- the ring an SGPR resource,
-// the row in the scalar offset, the lane's place a loop-invariant VGPR, no
-// 64-bit VALU address per store -- were built in round 8, brought the last
-// wave's group to the middle waves' VALU count, and measured 12 % slower:
-// 1652-1658 against 1875-1890 GCUPS, profiles/r8_helix_ab.jsonl. Not kept;
-// DESIGN.md 4.2 describes the form.)
 // v_bfi_b32 with an SGPR source for the selected bits
 __device__ __forceinline__ uint32_t vbfi_s(uint32_t mask, uint32_t a, uint32_t b) {
   uint32_t r;
   asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(mask), "s"(a), "v"(b));
   return r;
 }
-// V-space: the writer shifts its record instead of the reader:
-// a wave stores each position's {Iyz, best} where position k+1 reads it, and
-// lane 0's low halves carry the z = 0 face the reader needs -- which is the
-// writer's own H(t+2) (after its lap-wrap update): the reader, one row down,
-// reads the record two steps later at the same u. The reader then takes Iyz
-// and M from its record with no DPP + v_perm (4 VALU per step fewer); the
-// writer pays LDS / VMEM writes, no VALU (tools/pencil_emu.py shifted=True
-// replays it against the oracle). Measured SLOWER on MI355X and off: same-box
-// 512 x 256^3, 1651-1653 GCUPS against 1705-1706 without it, while the reads
-// alone (the writes left unshifted: wrong scores, timing only) give 1742-1745
-// -- the z-shift it removes is off the dependent path (+2 %), the split and
-// exec-masked writes cost more (profiles/r6g_helix_shr_ab.jsonl)
-#ifndef TSA_SHIFTED_REC
-#define TSA_SHIFTED_REC 0
-#endif
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void ring_st64(__amdgpu_buffer_rsrc_t r, uint32_t voff, int32_t soff, uint32_t lo,
-                                          uint32_t hi) {
-  __builtin_amdgcn_raw_buffer_store_b64((u32x2){lo, hi}, r, voff, soff, 0);
-}
-__device__ __forceinline__ void ring_st32(__amdgpu_buffer_rsrc_t r, uint32_t voff, int32_t soff, uint32_t v) {
-  __builtin_amdgcn_raw_buffer_store_b32(v, r, voff, soff, 0);
-}
-__device__ __forceinline__ void ring_st16(__amdgpu_buffer_rsrc_t r, uint32_t voff, int32_t soff, uint32_t v) {
-  __builtin_amdgcn_raw_buffer_store_b16((unsigned short)v, r, voff, soff, 0);
-}
-__device__ __forceinline__ void lds_w64_at(lds_u8 *base, int off, uint32_t lo, uint32_t hi) {
-  *(__attribute__((address_space(3))) uint64_t *)(base + off) = ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ void lds_w32_at(lds_u8 *base, int off, uint32_t v) {
-  *(__attribute__((address_space(3))) uint32_t *)(base + off) = v;
-}
-__device__ __forceinline__ void lds_w16_at(lds_u8 *base, int off, uint32_t v) {
-  *(__attribute__((address_space(3))) uint16_t *)(base + off) = (uint16_t)v;
-}
-// Ablation knobs (timing diagnostics only: the scores are WRONG when set):
-// TSA_ABL_ZOWN / TSA_ABL_ZREC replace the DPP + v_perm z-shift of the own
-// (Iz, Ixz) / the row-above (Iyz, M) messages by register moves, TSA_ABL_INJ
-// drops the x = 1 injection -- how much of the step each costs.
-#ifndef TSA_ABL_ZOWN
-#define TSA_ABL_ZOWN 0
-#endif
-#ifndef TSA_ABL_ZREC
-#define TSA_ABL_ZREC 0
-#endif
-#ifndef TSA_ABL_INJ
-#define TSA_ABL_INJ 0
-#endif
-// TSA_ABL_RING drops the lap-to-lap ring (1: the last wave's record stores and
-// wave 0's LDS-DMA fetches, wave 0 then reading stale slots; 2: the stores
-// only; 3: the fetches only) -- the ring's share of the step, timing only
-#ifndef TSA_ABL_RING
-#define TSA_ABL_RING 0
-#endif
-// cache policy of the ring (bit 0: the last wave's stores nt; bit 1: wave 0's
-// fetches sc1 nt instead of sc1)
-#ifndef TSA_RING_NT
-#define TSA_RING_NT 0
-#endif
-// V-space: wave 0 builds the y = 0 face records of its first lap from its own
-// H registers up to a switch step t_sw and fetches the ring only from there;
-// the prologue fills the dozen rows of steps [t_sw, lag) instead of the whole
-// ring (0: every row filled and fetched, 277 MB stored and 254 MB read back per
-// 512 x 256^3 launch for values that are formulas). Neutral on its own (1881-
-// 1898 against 1877-1898 GCUPS), +1.6 % once the barrier no longer waits for the
-// A read below: 1930-1947 against 1894-1922, eight interleaved bench passes
-// (profiles/r7_helix_ring_rows_ab.jsonl)
-#ifndef TSA_RING_FIRSTLAP
-#define TSA_RING_FIRSTLAP 1
-#endif
-// V-space: an even step reads the A codes of both steps after it, so the odd
-// step's barrier waits for its record writes alone (0: each step reads the
-// next one's, and every barrier's lgkmcnt(0) waits for that read's round trip);
-// +2.6 % (1937-1944 against 1881-1898 GCUPS, four passes, r7)
-#ifndef TSA_A_EVEN_READS
-#define TSA_A_EVEN_READS 1
-#endif
-// V-space: the record slots' and the A table's per-lane addresses held in
-// VGPRs (0: the compiler re-adds the lane's part to an SGPR base in every
-// four-step group, 2 VALU of 268; +0.4 % on average, 1937-1955 against 1937-
-// 1944 GCUPS, not resolved pass by pass, r7)
-#ifndef TSA_PIN_BASES
-#define TSA_PIN_BASES 1
-#endif
-// wave 0's per-step fetch of an M = 2 ring row as one statement: both 1 KiB
-// pieces through the saddr form (the row's SGPR base, the lane's two constant
-// VGPR offsets), M0 set from a 32-bit LDS address -- no per-step 64-bit VALU
-// address, no generic-to-LDS pointer check, one M0 save / restore: wave 0's
-// step 279 -> 271 VALU, 120 -> 80 SALU per four steps; batch +1.2-1.6 %
-// (round 6, profiles/r6n_helix_dma_saddr_ab.jsonl).
-// (TSA_RING_NT bit 1 applies to the TSA_DMA_SADDR=0 form.)
-#ifndef TSA_DMA_SADDR
-#define TSA_DMA_SADDR 1
-#endif
-// The forms TSA_REC_PREV applies to: wave 0 issues no ring fetch. A
-// global_load_lds lands in LDS whichever wave issues it, so waves 1 and 2 issue
-// the rows with dma16x2_saddr, at the first and the third step of the four-step
-// group (static steps: no run-time test in the loop), and wave 0 only reads its
-// xr0 slots. At such a step t wave 1 issues the row of step t + 6, wave 2 that
-// of step t + 7. The step barrier is the only synchronisation: the row of step
-// s + PD goes into slot s % PD in the barrier interval after the one in which
-// wave 0 read step s there, and at the step after an issue the issuer waits
-// with a counted vmcnt until only its two newest rows are in flight, before the
-// barrier that precedes the interval of the oldest one's step. Issue to use is
-// 5 to 6 steps. The issuers start PD steps before wave 0's switch step t_sw, so
-// they fill the pipeline too and nothing is primed. 0: wave 0 fetches its own
-// rows, PD steps ahead. Every pass of eight above every pass of the parent
-// together with TSA_BINJ_SGPR and TSA_RING_ST_SADDR, +1.2 and +1.7 % on two
-// boxes; alone +0.4 %, not resolved (profiles/r10_helix_fetch_ab.jsonl). Four
-// issuers with a row per group each, and wave 1 issuing all four rows, measured
-// slower than two and were not kept.
-#ifndef TSA_FETCH_SHARED
-#define TSA_FETCH_SHARED 1
-#endif
-// The forms TSA_REC_PREV applies to, last wave: the ring store's address as the
-// row's uniform base plus the lane's unsigned 32-bit offset, which the compiler
-// selects as the store's saddr form (0: a 64-bit VALU address per step)
-#ifndef TSA_RING_ST_SADDR
-#define TSA_RING_ST_SADDR 1
-#endif
-// The forms TSA_REC_PREV applies to: the x = 1 position's B code injected from
-// the SGPR it lives in (vbfi_s), as the H values are (0: through a VGPR operand,
-// which costs a v_mov per step)
-#ifndef TSA_BINJ_SGPR
-#define TSA_BINJ_SGPR 1
-#endif
+// An M = 2 ring row's fetch as one statement: both 1 KiB pieces through the
+// saddr form (the row's SGPR base, the lane's two constant VGPR offsets), M0 set
+// from a 32-bit LDS address -- no per-step 64-bit VALU address, no generic-to-
+// LDS pointer check, one M0 save / restore.
 // (only s_mov in the statement: an s_add would write SCC behind the compiler's back)
 __device__ __forceinline__ void dma16x2_saddr(const uint8_t *sbase, uint32_t voff0, uint32_t voff1,
                                               uint32_t lds0, uint32_t lds1) {
@@ -260,25 +131,6 @@ __device__ __forceinline__ void dma16x2_saddr(const uint8_t *sbase, uint32_t vof
       : "=&s"(keep)
       : "v"(voff0), "v"(voff1), "s"(sbase), "s"(lds0), "s"(lds1)
       : "memory");
-}
-__device__ __forceinline__ void dma16_nt(const void *gsrc, const void *lds_dst) {
-  unsigned keep;
-  const unsigned dst = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)lds_dst;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off sc1 nt\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(dst))
-      : "memory");
-}
-template <int M>
-__device__ __forceinline__ void zmove_abl(uint32_t (&v)[M], const uint32_t (&src)[M]) {
-#pragma unroll
-  for (int i = M - 1; i >= 1; --i) v[i] = src[i - 1];
-  v[0] = src[M - 1];
 }
 // A-table entries past P + 128M repeating its start (the table is periodic in
 // P): the V-space loop reads a four-step group's A codes at constant offsets
@@ -312,17 +164,19 @@ static PencilGeom pencil_geom(int32_t max_la, int32_t max_lc, bool no_two = fals
   g.two = !no_two && helix_two(max_lc);
   g.P = std::max(max_la, g.two ? 64 : 128 * g.M);
   g.P = (g.P + g.M - 1) / g.M * g.M;  // even for M = 2: the x = 1 register is PH ^ (w & 1)
-  if (g.M == 2 && !g.two && TSA_EV_STATIC) g.P = (g.P + 3) / 4 * 4;  // TSA_EV_STATIC
+  // M = 2: a multiple of 4, so the half-mask and lap-wrap events fall on one static
+  // step of a wave's four-step group (EV_SKIP in step)
+  if (g.M == 2 && !g.two) g.P = (g.P + 3) / 4 * 4;
   g.R = g.P + RING_EXTRA;
   g.ring_bytes_per_triple = (int64_t)g.R * g.M * 64 * REC_BYTES;
   return g;
 }
-// vs: the V-space instantiation, whose M = 2 form (TSA_A_B64) also keeps the
+// vs: the V-space instantiation, whose M = 2 form (A_B64) also keeps the
 // A table's copy shifted by one entry after fin; the other forms do not
 static size_t helix_lds(int M, int NW, int32_t P, int32_t max_lb, bool vs) {
   const size_t a_tab = 4 * ((size_t)P + 128 * M + A_PAD);
   return (size_t)(NW - 1) * 2 * helix_skew(M) * M * 1024 + (size_t)helix_pd(M) * M * 1024 + a_tab +
-         4 * (((size_t)max_lb + 3) & ~(size_t)3) + (size_t)M * 512 + (vs && M == 2 && TSA_A_B64 ? a_tab : 0);
+         4 * (((size_t)max_lb + 3) & ~(size_t)3) + (size_t)M * 512 + (vs && M == 2 ? a_tab : 0);
 }
 
 // The factored messages widen each target's highest-penalty group to all seven
@@ -482,13 +336,13 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
   uint32_t *sB = (uint32_t *)((uint8_t *)sA2 + lds_a);
   uint32_t *fin = (uint32_t *)((uint8_t *)sB + lds_b);
   uint32_t *sA2s = (uint32_t *)((uint8_t *)fin + M * 512);  // A_B64: sA2 shifted by one entry
-  constexpr bool A_B64 = VS && M == 2 && TSA_A_B64;
+  constexpr bool A_B64 = VS && M == 2;  // a step's A codes as one ds_read_b64 (load_a_pair)
 
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   static_assert(!TWO || M == 1, "two triples per wave: 64 positions, M = 1");
   static_assert(!VS || (F16 && M <= 2), "V-space: the f16 helix with the four-step loop");
-  static_assert(!VI || (VS && M == 2 && !TWO && helix_skew(M) == 2 && !TSA_H_TAB && !TSA_SHIFTED_REC && !TSA_PREINJ),
+  static_assert(!VI || (VS && M == 2 && !TWO && helix_skew(M) == 2),
                 "integer patterns: the V-space M = 2 helix at skew 2");
   static_assert(!END || (F16 && !TWO && M <= 2), "end search: the f16-class helix, one triple per workgroup");
   constexpr uint32_t SYMC = VI ? 1u : SYM0;  // symbol codes SYMC << s
@@ -509,15 +363,12 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
   constexpr int KS = TWO ? 64 : 128 * M;  // positions (per half in TWO)
   uint32_t ones = F16 ? 0x08000800u : 0x00010001u;  // f16: match indicator 2^-13
   asm volatile("" : "+v"(ones));                     // keep it in a VGPR (VOP3P operand)
-  constexpr bool SHR = VS && TSA_SHIFTED_REC && !TSA_ABL_ZREC;  // writer-shifted records (off)
   const PencilArgs pv = F16 ? pa : pin_score_consts(pa);
   uint32_t fsv = pa.f_single, fpv = pa.f_pair;  // VGPR copies for v_bfi_b32 / v_pk_mad_u16
   uint32_t sbcv = pa.h_sbc, kdv = pa.h_kd, k0v = pa.h_k0, one1 = 0x00010001u;
   uint32_t hmLo = TWO ? 0xFFFFFFFFu : 0x0000FFFFu, hmHi = 0xFFFF0000u, zero = 0u;
-  // (SHR keeps V-space under 128 VGPRs by leaving unpinned what only the per-lap
-  // row terms read -- sbcv / kdv / k0v / one1 -- and the half masks)
-  if constexpr (!SHR) asm volatile("" : "+v"(fsv), "+v"(fpv), "+v"(sbcv), "+v"(kdv), "+v"(k0v), "+v"(one1));
-  if constexpr (!SHR) asm volatile("" : "+v"(hmLo), "+v"(hmHi), "+v"(zero));
+  asm volatile("" : "+v"(fsv), "+v"(fpv), "+v"(sbcv), "+v"(kdv), "+v"(k0v), "+v"(one1));
+  asm volatile("" : "+v"(hmLo), "+v"(hmHi), "+v"(zero));
   // a[i] of this lane at step t is sA2[(t-w) mod P + ZT - M lane - i]
   const uint32_t a_lane = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)sA2 +
                           4u * (uint32_t)(ZT - M * lane - (M - 1));
@@ -528,28 +379,20 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
   uint8_t *rd_wave = w > 0 ? xr + (w - 1) * HNSL * SLOT_BYTES : xr0;
   const lds_u8 *rd_base = to_lds(rd_wave + lane * REC_BYTES);
   lds_u8 *wr_base = to_lds(xr + w * HNSL * SLOT_BYTES + lane * REC_BYTES);
-  // RP (TSA_REC_PREV): the record of the previous position's last register,
-  // lane - 1's (lane 63's for lane 0), where a lane reads register 0's {Iyz, best}
-  constexpr bool RP = VS && M == 2 && !TWO && HSK == 2 && TSA_REC_PREV && !SHR && !TSA_ABL_ZREC;
+  // RP: a reader takes {Iyz, best} of the row above from the record of position
+  // k - 1 by the address of its LDS read, not from its own record through a DPP
+  // shift. rd_prev: the record of the previous position's last register, lane -
+  // 1's (lane 63's for lane 0), where a lane reads register 0's {Iyz, best}.
+  // The same instantiations (the flagship's) have waves 1 and 2 issue wave 0's
+  // ring fetches, store the ring rows in the saddr form and inject the B code
+  // from its SGPR: RP names them all.
+  constexpr bool RP = VS && M == 2 && !TWO && HSK == 2;
   const lds_u8 *rd_prev = to_lds(rd_wave + ((lane + 63) & 63) * REC_BYTES);
-  // TSA_PIN_BASES: all held in VGPRs (left alone, the compiler keeps the wave's
-  // part in an SGPR and adds the lane's part again in every four-step group)
-  if constexpr (VS && !SHR && TSA_PIN_BASES) asm volatile("" : "+v"(rd_base), "+v"(wr_base));
-  if constexpr (RP && TSA_PIN_BASES) asm volatile("" : "+v"(rd_prev));
-  // HT (TSA_H_TAB): H in SGPRs, from the constant table (a function-local
-  // constant: a private object at a pc-relative address, where a __constant__
-  // variable is visible to the host and reached through a loaded address)
-  static constexpr HTable H_TABLE = make_h_table();
-  constexpr bool HT = VS && M == 2 && !TWO && HSK == 2 && TSA_H_TAB && TSA_EV_STATIC && TSA_HM_TRACK;
-  // SHR (TSA_SHIFTED_REC): the writes of a shifted record. Register M-1's
-  // {Iyz, best} go to lane + 1's pair 0 (lanes 0..62); lane 0's pair-0
-  // {Iyz, best} take lane 63's register M-1 low halves in their high halves
-  // (lane 63 alone, through wrH / the ring resource based 63 records lower)
-  // and the z = 0 face in their low halves (lane 0 alone, once the step's
-  // lap-wrap update has set it). Exec-masked single-lane writes: no per-lane
-  // offset VGPRs (the kernel sits at the 128-VGPR edge of 4 waves per SIMD).
-  lds_u8 *wrH = to_lds(xr + w * HNSL * SLOT_BYTES + 10);  // lane 0's pair-0 Iyz high half
-  uint32_t own = (uint32_t)lane * REC_BYTES;              // the lane's record in a ring row
+  // V-space: all held in VGPRs (left alone, the compiler keeps the wave's part
+  // in an SGPR and adds the lane's part again in every four-step group)
+  if constexpr (VS) asm volatile("" : "+v"(rd_base), "+v"(wr_base));
+  if constexpr (RP) asm volatile("" : "+v"(rd_prev));
+  uint32_t own = (uint32_t)lane * REC_BYTES;  // the lane's record in a ring row
   const int32_t nunit = TWO ? (n + 1) / 2 : n;  // workgroup units: triples, or pairs
   for (int unit = blockIdx.x; unit < nunit; unit += gridDim.x) {
     const int tri = TWO ? 2 * unit : unit;
@@ -564,10 +407,6 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
     const int32_t lc1 = TWO ? (int32_t)(of1[3] - q2) : lc;
     const int32_t lbm = max(lb, lb1);
     uint8_t *ring = ring_base + (int64_t)blockIdx.x * ring_stride;
-    // SHR: the ring as a buffer resource (the last wave's record stores)
-    const __amdgpu_buffer_rsrc_t rs_ring = __builtin_amdgcn_make_buffer_rsrc(ring, (short)0, 0x7FFFFFFF, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_ring63 =
-        __builtin_amdgcn_make_buffer_rsrc(ring - 63 * REC_BYTES, (short)0, 0x7FFFFFFF, 0x00020000);
 
     // ---- stage A codes (padded to P, halves k/k+64M or, TWO, the two triples) and
     // B; face records in the ring
@@ -596,11 +435,11 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
     // (step lag). Only the rows of steps [t_sw, lag) are filled here: every
     // other row wave 0 fetches was written by the last wave of this unit, so a
     // workspace may hold anything (an earlier unit's or launch's rows) at entry
-    constexpr bool FIRSTLAP = VS && TSA_RING_FIRSTLAP;
+    constexpr bool FIRSTLAP = VS;
     const int32_t t_sw = FIRSTLAP ? max(lag - PD, 0) & ~3 : 0;
-    // SF (TSA_FETCH_SHARED): middle waves issue wave 0's ring fetches. (M = 2:
+    // The RP forms share wave 0's ring fetches: waves 1 and 2 issue them. (M = 2:
     // P >= 256, so lag >= 242 and t_sw >= 2 PD: the issuers' first groups exist)
-    constexpr bool SF = RP && FIRSTLAP && TSA_FETCH_SHARED && TSA_DMA_SADDR && PD == 8 && NW >= 4;
+    static_assert(!RP || (PD == 8 && NW >= 4), "shared fetches: two issuers, eight slots");
     if constexpr (FIRSTLAP) {
       // row 0's face cells as wave 0 meets them at step tr: x + z = tr + 2 for
       // every position ({Iy, Ixy, Iyz, best} = lam q - lam, lam q x 3); step tr
@@ -611,18 +450,10 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
         const uint32_t f1 = h_bits(pa.lam * (tr + 1)), f2 = h_bits(pa.lam * (tr + 2));
         ((uint4 *)ring)[(int64_t)(R - lag + tr) * (M * 64) + i % (M * 64)] = make_uint4(f1, f2, f2, f2);
       }
-    } else {
+    } else {  // the message forms: every row holds the constant y = 0 face
       const uint4 face = make_uint4(pa.f_single, pa.f_pair, pa.f_pair, 0u);
       const int64_t n16 = (int64_t)R * M * 64;
-      for (int64_t i = threadIdx.x; i < n16; i += 64 * NW) {
-        if constexpr (VS) {  // every row (TSA_RING_FIRSTLAP=0): ring row r is the row of step (r + lag) mod R
-          const int32_t tr = (int32_t)((i / (M * 64) + lag) % R);
-          const uint32_t f1 = h_bits(pa.lam * (tr + 1)), f2 = h_bits(pa.lam * (tr + 2));
-          ((uint4 *)ring)[i] = make_uint4(f1, f2, f2, f2);
-        } else {
-          ((uint4 *)ring)[i] = face;
-        }
-      }
+      for (int64_t i = threadIdx.x; i < n16; i += 64 * NW) ((uint4 *)ring)[i] = face;
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();
@@ -654,7 +485,6 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
     // position-0 bookkeeping (wave-uniform): u0 = t - w
     int32_t xpos0 = (P - ((HSK * w) % P)) % P;  // (t - HSK w) mod P at t = 0
     int32_t lap0 = w == 0 ? 0 : -1;     // floor((t - w) / P)
-#if TSA_HM_TRACK
     // bfi half mask of the x = 1 position xpos0 -- low half below 64M, high
     // half below KS, none from KS up to the lap wrap (P > KS) -- switched at
     // those events (one compare per step) rather than tested every step
@@ -664,7 +494,6 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
     auto ev_of = [&](int32_t xp) -> int32_t { return xp < 64 * M ? 64 * M : xp < KS ? KS : P; };
     uint32_t hmCur = hm_of(xpos0);
     int32_t next_ev = ev_of(xpos0);
-#endif
     // B code of row lap0*NW+w+1, taken by the position at x = 1 (0 past LB)
     auto b_of_lap = [&](int32_t lp) -> uint32_t {
       const int32_t r = lp * NW + w;
@@ -675,7 +504,7 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
     // a position copies them when it reaches x = 1 (recomputed once per lap)
     uint32_t SBCn[M], Kn[M], DMBn = 0;
     auto row_terms = [&]() {
-      if constexpr (F16 && TSA_ROW_NEXT) {
+      if constexpr (F16) {
         // V-space: the [a=b] terms multiply the symbol code itself (a & b, no
         // min): DMB = dm / code(b) and, RTL, K = (d0 + [b=c] d1) / code(b)
         uint32_t kb0 = k0v, kbd = kdv;
@@ -709,74 +538,27 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
 
     // VS: Hr[s & 3] = H(s) = lam * (y + xpos0) at step s (y: position 0's row,
     // 1-based) -- the x = 0 face at the x = 1 position and, one and two steps
-    // ahead, the z = 0 face of position 0; step s sets H(s + 2): one v_pk_add,
-    // or (HT) the table's entry, reset at a wrap
+    // ahead, the z = 0 face of position 0; step s sets H(s + 2): one v_pk_add (VI:
+    // a scalar add), reset at a wrap
     uint32_t Hr[4] = {0u, 0u, 0u, 0u};
     auto hq_at = [&](int32_t s) -> int32_t {
       const int32_t u = s - HSK * w;
       const int32_t lp = u >= 0 ? u / P : -((P - 1 - u) / P);
       return pa.lam * (lp * NW + w + 1 + (u - lp * P));
     };
-    // HT: the table's entry of lam q (wave-uniform: a scalar load); the unsigned
-    // clamp keeps any q, a padding position's or a negative one, inside the table
-    auto h_tab = [&](int32_t q) -> uint32_t {
-      return H_TABLE.v[min((uint32_t)q, (uint32_t)H_TAB_SAT)];
-    };
-    // four values lam q0, lam q0 + lam, ...: contiguous entries for lam = 1 (the
-    // RTL's constants), read as one four-dword load -- a scalar load's address
-    // needs dword alignment only, whatever its width; an index clamped to
-    // H_TAB_SAT + 1 reads the saturated tail (H_TAB_N). l1: lam = 1 is known
-    // at compile time (the loop's lam = 1 version, see run below): a run-time
-    // test here would merge the two forms' registers right after the loads,
-    // and the copies would wait for them
-    auto h_tab4 = [&](auto l1, int32_t q0, uint32_t (&out)[4]) {
-      if constexpr (decltype(l1)::value) {
-        typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-        const u32x4_a4 v = *(const u32x4_a4 *)&H_TABLE.v[min((uint32_t)q0, (uint32_t)H_TAB_SAT + 1u)];
-        out[0] = v.x, out[1] = v.y, out[2] = v.z, out[3] = v.w;
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) out[j] = h_tab(q0 + j * pa.lam);
-      }
-    };
-    // HT: hg = lam q of the H the group's last step sets (no wrap: + 4 lam per
-    // group); Hn the four values the group's steps set, Hp the next group's
-    int32_t hg = 0;
-    uint32_t Hn[4] = {0u, 0u, 0u, 0u}, Hp[4] = {0u, 0u, 0u, 0u};
     if constexpr (VS) {
       // the step-0 injection's (0, y-1, z-1) face is H(0) - lam (wave 0 starts
       // its first row at step 0 with no wrap that would have set it)
-      if constexpr (HT) {
-        Hr[0] = h_tab(hq_at(0));
-        Hr[1] = h_tab(hq_at(1));
-        Hr[3] = h_tab(hq_at(0) - pa.lam);
-        hg = hq_at(1);  // the first group adds its 4 lam (group_bases)
-        h_tab4(std::false_type{}, hg + pa.lam, Hp);
-      } else {
-        Hr[0] = h_bits(hq_at(0));
-        Hr[1] = h_bits(hq_at(1));
-        if constexpr (VI) Hr[3] = Hr[0] - pa.i_lam;
-        else Hr[3] = U(H(Hr[0]) - H(pa.v_lam));
-      }
+      Hr[0] = h_bits(hq_at(0));
+      Hr[1] = h_bits(hq_at(1));
+      if constexpr (VI) Hr[3] = Hr[0] - pa.i_lam;
+      else Hr[3] = U(H(Hr[0]) - H(pa.v_lam));
       if (w == 0) {  // position 0's z = 0 faces at steps 0 and 1 (as if shifted in at steps -1, -2)
 #pragma unroll
         for (int i = 0; i < M; ++i) {
           shIz[i] = svIyz[i] = svM[1][i] = Hr[0];
           shIxz[1][i] = Hr[1];
         }
-      }
-    }
-    // SHR: no record precedes wave 1's first steps: before reading them, wave 1
-    // seeds lane 0's shifted {Iyz, best} in wave 0's slots of steps -2 and -1
-    // (slots 2, 3, which wave 0 first writes after the first barrier) with the
-    // z = 0 face its position 0 takes from them (H_0(0), H_0(1): lam, 2 lam);
-    // the reader's face used to come from its own z-shift, whatever the slot held
-    if constexpr (SHR) {
-      if (w == 1 && lane == 0) {
-        uint32_t *s0 = (uint32_t *)(xr + 8);
-        const uint32_t f1 = h_bits(pa.lam), f2 = h_bits(2 * pa.lam);
-        s0[2 * SLOT_BYTES / 4] = s0[2 * SLOT_BYTES / 4 + 1] = f1;
-        s0[3 * SLOT_BYTES / 4] = s0[3 * SLOT_BYTES / 4 + 1] = f2;
       }
     }
     // wave 0: prime the LDS-DMA pipeline with the rows of steps t0 .. t0 + PD - 1
@@ -796,13 +578,13 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
     if constexpr (!FIRSTLAP) {
       if (w == 0) prime(0);
     }
-    // SF: issuer w (1 or 2) takes the rows of the steps = iss_j (mod 2). It issues
+    // RP: issuer w (1 or 2) takes the rows of the steps = iss_j (mod 2). It issues
     // from group t_iss on, at step t the row of step t + 6 + iss_j; the first row
     // wave 0 reads is the second it issues (the very first, of step t_sw - 2 +
     // iss_j, lands in a slot nobody reads). The other waves never get there.
     const int32_t iss_j = w - 1;
     int32_t t_iss = 0x7FFFFFFF;
-    if constexpr (SF) {
+    if constexpr (RP) {
       if (w == 1 || w == 2) {
         t_iss = t_sw - PD;
         dma_row = ((t_iss + 6 + iss_j - lag) % R + R) % R;
@@ -810,16 +592,16 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
     }
     // byte offset of step (6 + iss_j)'s slot; step t's issue adds t slots (mod PD)
     const uint32_t iss_slot0 = (uint32_t)((6 + iss_j) * SLOT_BYTES);
-    const uint32_t dvo0 = (uint32_t)lane * REC_BYTES, dvo1 = dvo0 + PAIR_BYTES;  // TSA_DMA_SADDR
+    const uint32_t dvo0 = (uint32_t)lane * REC_BYTES, dvo1 = dvo0 + PAIR_BYTES;  // dma16x2_saddr's lane offsets
     const uint32_t xr0_lds = __builtin_amdgcn_readfirstlane(
         (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)xr0);
     uint32_t a_nx[M];                            // A codes of the coming step (A_EVEN: the coming odd step)
     // A_EVEN: the coming even step's. An even step reads the codes of both steps
     // after it, so no LDS read is pending at the barrier that ends the odd one
-    constexpr bool A_EVEN = VS && TSA_A_EVEN_READS && TSA_A_PREFETCH;
+    constexpr bool A_EVEN = VS;
     uint32_t a_ev[M];
     if constexpr (A_EVEN) load_a<M>(a_lane + 4u * (uint32_t)xpos0, a_ev);
-    else if constexpr (TSA_A_PREFETCH) load_a<M>(a_lane + 4u * (uint32_t)xpos0, a_nx);
+    else load_a<M>(a_lane + 4u * (uint32_t)xpos0, a_nx);
     int32_t st_row = 0;                          // ring row written at step t (last wave)
     uint32_t abase = a_lane;                     // VS: A address of the group's first step
     // A_B64: the same entry in the shifted copy
@@ -830,49 +612,21 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
     // VS: the step whose cell is the final one, in this wave (-1: none)
     const int32_t t_fin = w == w_f ? T - 1 : -1;
     // the x = 1 mask kept from the even step of a pair (step, MASK_PAIRS)
-    constexpr bool MASK_PAIRS = VS && M == 2 && HSK == 2 && TSA_HM_TRACK;
+    constexpr bool MASK_PAIRS = VS && M == 2 && HSK == 2;
     uint32_t m1_pair = 0u;
-    constexpr bool PRE = VS && TSA_PREINJ && !TSA_ABL_INJ && TSA_HM_TRACK;
-    // PRE: the injection of the step of phase PQN (the next one), into the
-    // registers that step reads: Ix (own), Ixy (the row above's record), Ixz and
-    // M (the z-shifted double buffers of its parity), and the per-row terms
-    auto vs_inject = [&](auto pqc) {
-      constexpr int PQN = decltype(pqc)::value;
-      constexpr int PHN = PQN & 1;
-      constexpr int ISN = M == 2 ? PHN : -1;  // skew 2, even P: the x = 1 register is the step's parity
-      int32_t ls, is, hs;
-      pos_split<M>(xpos0, ls, is, hs);
-      uint32_t m1;
-      if constexpr (MASK_PAIRS && (PQN & 1)) {
-        m1 = m1_pair;
-      } else {
-        asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(m1) : "v"(hmCur), "s"(1ull << ls));
-        if constexpr (MASK_PAIRS) m1_pair = m1;
-      }
-#pragma unroll
-      for (int i = 0; i < M; ++i) {
-        if (ISN >= 0 ? i == ISN : i == is) {
-          if constexpr (HT) {
-            oIx[i] = vbfi_s(m1, Hr[PQN & 3], oIx[i]);
-            svIxy[i] = vbfi_s(m1, Hr[PQN & 3], svIxy[i]);
-            shIxz[PHN][i] = vbfi_s(m1, Hr[PQN & 3], shIxz[PHN][i]);
-            svM[PHN][i] = vbfi_s(m1, Hr[(PQN + 3) & 3], svM[PHN][i]);
-          } else {
-            oIx[i] = vbfi(m1, Hr[PQN & 3], oIx[i]);
-            svIxy[i] = vbfi(m1, Hr[PQN & 3], svIxy[i]);
-            shIxz[PHN][i] = vbfi(m1, Hr[PQN & 3], shIxz[PHN][i]);
-            svM[PHN][i] = vbfi(m1, Hr[(PQN + 3) & 3], svM[PHN][i]);
-          }
-          b[i] = vbfi(m1, binj, b[i]);
-          SBC[i] = vbfi(m1, SBCn[i], SBC[i]);
-          K[i] = vbfi(m1, Kn[i], K[i]);
-          DMB[i] = vbfi(m1, DMBn, DMB[i]);
-        }
-      }
-    };
+    // Called by no instantiation, and kept for the compiler's sake alone. The step
+    // names this lambda once, in a branch no phase takes, where it used to name
+    // the retired table fetch of the face values. Without that capture every
+    // kernel still gets the same instructions, but in the 19 f16-class ones the
+    // two to five register copies of binj / SBCn / Kn ahead of the step loop come
+    // out in another order; with it each kernel's code is byte for byte what it
+    // was with the build switches. Take both lines out with the next change that
+    // moves the kernel's code anyway.
+    auto copy_order = [&](auto z) { return pa.lam + lane + decltype(z)::value; };
     // One step; PH = t & 1 picks the register roles and the LDS record slots,
-    // ROLE the wave's place in the lap (0: wave 0, reads the ring; 2: the last
-    // wave, writes it; 1: the others), so the loop body has no role branches.
+    // ROLE the wave's place in the lap (0: wave 0, reads the ring; 3: wave 0 in
+    // its first lap, before step t_sw; 2: the last wave, writes the ring; 1: the
+    // others), so the loop body has no role branches.
     auto step = [&](auto ph, auto role, int32_t t, auto fin_step) {
       // ph = t & 3 (or -1: slot phase at run time); PH = t & 1 picks the registers
       constexpr int PQ = decltype(ph)::value;
@@ -882,26 +636,18 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
       // M = 2 with even P: the x = 1 position's register (t - w) mod 2 is
       // PH ^ (w & 1), a compile-time constant for a wave of known parity
       constexpr int WPAR = ((decltype(role)::value >> 2) & 3) - 1;  // -1: unknown
-      constexpr bool L1 = (decltype(role)::value >> 4) & 1;  // HT: the loop's lam = 1 version
       constexpr int ISC = (M == 2 && WPAR >= 0) ? (HSK == 2 ? PH : PH ^ WPAR) : -1;
       constexpr bool FIN = decltype(fin_step)::value;  // the last step (t == T-1)
-      // SF: this wave issues ring rows in this loop (role bit 5): at the even
+      // RP: this wave issues ring rows in this loop (role bit 5): at the even
       // steps; the odd step after waits for the oldest row before its barrier
-      constexpr bool ISS = SF && ((decltype(role)::value >> 5) & 1) && TSA_ABL_RING != 1 && TSA_ABL_RING != 3;
+      constexpr bool ISS = RP && ((decltype(role)::value >> 5) & 1);
       constexpr bool ISS_AT = ISS && PQ >= 0 && PQ < 4 && (PQ & 1) == 0;
       constexpr bool ISS_WAIT = ISS && PQ >= 0 && PQ < 4 && (PQ & 1) == 1;
       // this step's A codes (LDS table) and the B code of position x = 1
       uint32_t a[M];
-      if constexpr (TSA_A_PREFETCH) {
 #pragma unroll
-        for (int i = 0; i < M; ++i) a[i] = (A_EVEN && PH == 0) ? a_ev[i] : a_nx[i];
-      } else {
-        load_a<M>(a_lane + 4u * (uint32_t)xpos0, a);
-      }
-      // HT: the next group's four H values, fetched at the top of the group's
-      // third step: the scalar loads return with this step's record reads, and
-      // the next step's lgkmcnt(0) before its barrier covers them in any case
-      if constexpr (HT && PQ == 2) h_tab4(std::bool_constant<L1>{}, hg + pa.lam, Hp);
+      for (int i = 0; i < M; ++i) a[i] = (A_EVEN && PH == 0) ? a_ev[i] : a_nx[i];
+      if constexpr (PQ == 99) copy_order(ph);  // no phase is 99: see copy_order
       // ---- receive the wave-above record of step t-1
       // RP: {Iy, Ixy} of the lane's own record, {Iyz, best} of position k - 1's
       // (rec[i].z / .w then hold the values already shifted, but for lane 0's
@@ -909,7 +655,7 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
       // register 1's; register 0's are lane - 1's register M - 1
       uint4 rec[M];
       [[maybe_unused]] auto read_prev = [&](const lds_u8 *own_b, const lds_u8 *prev_b, int off) {
-        static_assert(!RP || M == 2, "TSA_REC_PREV: the M = 2 helix");
+        static_assert(!RP || M == 2, "reads at position k - 1: the M = 2 helix");
         const uint4 r0 = lds_read16_at(own_b, off);
         const uint2 r1 = lds_read8_at(own_b, off + PAIR_BYTES);
         const uint2 rp = lds_read8_at(prev_b, off + (M - 1) * PAIR_BYTES + 8);
@@ -919,9 +665,8 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
       if constexpr (ROLE == 0 && RP) {
         // the slot of step t is (t % PD): r0_own / r0_prev hold the group's part
         // (PD = 8, two groups), the step's is a constant offset
-        static_assert(!RP || PD == 8, "TSA_REC_PREV: wave 0's slots as two groups of four");
-        // (SF: the issuer waited for the row before the barrier this step follows)
-        if constexpr (!SF) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(M * (PD - 1)) : "memory");
+        static_assert(!RP || PD == 8, "reads at position k - 1: wave 0's slots as two groups of four");
+        // (no vmcnt wait: the issuer waited for the row before the barrier this step follows)
         read_prev(r0_own, r0_prev, (PQ & 3) * SLOT_BYTES);
       } else if constexpr (ROLE == 0) {
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(M * (PD - 1)) : "memory");
@@ -959,10 +704,9 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
       // ---- x == 1 at position k* = (t - w) mod P: its x-1 inputs are the x = 0
       // face (EN_i==1&&EN==0 gating, src/PE_1cyc.v:164-178,196-202,212-218), and
       // it starts row lap0*NW+w+1, whose B symbol it takes here.
-      if (!PRE && !TSA_ABL_INJ && (TSA_HM_TRACK || xpos0 < KS)) {  // (tracked: hmCur is 0 past KS)
+      {  // (hmCur is 0 past KS: nothing is selected there)
         int32_t ls, is, hs;
         pos_split<M>(xpos0, ls, is, hs);
-#if TSA_HM_TRACK
         uint32_t m1;
         // M = 2, skew 2: xpos0 has t's parity, so the odd step of a pair
         // injects the same lane and half as the even one (register 1 after
@@ -974,18 +718,13 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
           asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(m1) : "v"(hmCur), "s"(1ull << ls));
           if constexpr (MASK_PAIRS) m1_pair = m1;
         }
-#elif TSA_LANE_MASK
-        const uint32_t m1 = lane_half_mask(ls, hs, hmLo, hmHi);
-#else
-        const uint32_t m1 = lane == ls ? (TWO ? 0xFFFFFFFFu : hs ? 0xFFFF0000u : 0x0000FFFFu) : 0u;
-#endif
 #pragma unroll
         for (int i = 0; i < M; ++i) {
           if (ISC >= 0 ? i == ISC : i == is) {
             if constexpr (VS) {  // faces (0,y,z), (0,y-1,z), (0,y,z-1): lam(y+z-1); (0,y-1,z-1): one lam less
               // (VI: H is a wave-uniform integer a scalar add advances, so it
               // lives in SGPRs with no load, and the bfi reads it from there)
-              if constexpr (HT || VI) {
+              if constexpr (VI) {
                 inIx[i] = vbfi_s(m1, Hr[PQ & 3], inIx[i]);
                 inIxy[i] = vbfi_s(m1, Hr[PQ & 3], inIxy[i]);
                 inIxz[i] = vbfi_s(m1, Hr[PQ & 3], inIxz[i]);
@@ -1003,34 +742,26 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
               inM[i] = vbfi(m1, zero, inM[i]);
             }
             // (RP forms: binj is wave-uniform and lives in an SGPR; the bfi reads it there)
-            if constexpr (RP && TSA_BINJ_SGPR) b[i] = vbfi_s(m1, binj, b[i]);
+            if constexpr (RP) b[i] = vbfi_s(m1, binj, b[i]);
             else b[i] = vbfi(m1, binj, b[i]);
-            if constexpr (F16) {  // the new row's per-row terms
-#if TSA_ROW_NEXT
+            if constexpr (F16) {  // the new row's per-row terms (row_terms)
               SBC[i] = vbfi(m1, SBCn[i], SBC[i]);
               K[i] = vbfi(m1, Kn[i], K[i]);
               if constexpr (VS) DMB[i] = vbfi(m1, DMBn, DMB[i]);
-#else
-              const uint32_t e01 = pk_eq1(b[i], c[i], one1);
-              SBC[i] = pk_mad(e01, sbcv, 0u);
-              K[i] = pk_mad(e01, kdv, k0v);
-#endif
             }
           }
         }
       }
       // keep the per-row registers in place across the branches above (without
       // this the allocator copies b into a fresh pair every step)
-#if TSA_PIN_ROW
 #pragma unroll
       for (int i = 0; i < M; ++i) asm volatile("" : "+v"(b[i]), "+v"(SBC[i]), "+v"(K[i]), "+v"(DMB[i]));
-#endif
       uint32_t oIy[M], oIxy[M], oIyz[M], oBest[M], oIz[M], oIxz[M], nIx[M];
       // Priority 0 for the cell arithmetic, 1 for the send/shift/barrier tail:
       // VALU issue goes by priority then age, so without this the oldest waves
       // of a SIMD finish each step first and idle at the barrier (+3-4 %).
-      if constexpr (TSA_SETPRIO) __builtin_amdgcn_s_setprio(0);
-      if constexpr (TSA_SCHED_FENCE) __builtin_amdgcn_sched_barrier(0);  // keep the arithmetic between the two
+      __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_sched_barrier(0);  // keep the arithmetic between the two
       if constexpr (VI)
         cell_messages_vi<M, SOP>(a, b, c, SBC, K, DMC, DMB, pv, inIx, inIy, inIz, inIxy, inIyz, inIxz, inM, nIx,
                                  oIy, oIz, oIxy, oIyz, oIxz, oBest);
@@ -1044,8 +775,8 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
         cell_messages<M, SOP ? 1 : 0>(a, b, c, ones, pv, inIx, inIy, inIz, inIxy, inIyz, inIxz,
                                       inM, nIx, oIy, oIz, oIxy, oIyz, oIxz, oBest);
 
-      if constexpr (TSA_SCHED_FENCE) __builtin_amdgcn_sched_barrier(0);
-      if constexpr (TSA_SETPRIO) __builtin_amdgcn_s_setprio(1);
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_setprio(1);
       // ---- the final cell (src/TriAlign_1cyc.v:141-142,342-345) is in wave w_f's
       // last step; it is read back after the loop
       if constexpr (END) {  // no corner capture: the keys are folded after the record is sent
@@ -1064,27 +795,12 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
         }
       }
 
-      // ---- send this step's record to the wave below (or the ring); SHR: after
-      // the lap-wrap update below, which sets the face it carries
+      // ---- send this step's record to the wave below (or the ring)
       if constexpr (ROLE != 2) {
         const int off = (HSK == 2 ? q : PH) * SLOT_BYTES;
-        if constexpr (!SHR) {
 #pragma unroll
-          for (int i = 0; i < M; ++i)
-            lds_write16_at(wr_base, off + i * PAIR_BYTES, make_uint4(oIy[i], oIxy[i], oIyz[i], oBest[i]));
-        } else {  // shifted (lane 0's face halves after the lap-wrap update below)
-#pragma unroll
-          for (int i = 0; i < M; ++i) {
-            lds_w64_at(wr_base, off + i * PAIR_BYTES, oIy[i], oIxy[i]);
-            if (i + 1 < M) lds_w64_at(wr_base, off + (i + 1) * PAIR_BYTES + 8, oIyz[i], oBest[i]);
-          }
-          if (lane < 63) {
-            lds_w64_at(wr_base, off + REC_BYTES + 8, oIyz[M - 1], oBest[M - 1]);
-          } else if constexpr (!TWO) {
-            lds_w16_at(wrH, off, oIyz[M - 1]);
-            lds_w16_at(wrH, off + 4, oBest[M - 1]);
-          }
-        }
+        for (int i = 0; i < M; ++i)
+          lds_write16_at(wr_base, off + i * PAIR_BYTES, make_uint4(oIy[i], oIxy[i], oIyz[i], oBest[i]));
       } else {
         // Positions that have not started (u = t - w - k < 0) must publish the
         // y = 0 face: wave 0 reads this row as "row y0-1" during its lap 0.
@@ -1104,44 +820,16 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
             oBest[i] = bfi(m, fb, oBest[i]);
           }
         }
-        if constexpr (TSA_ABL_RING == 1 || TSA_ABL_RING == 2) {
-        } else if constexpr (!SHR) {
-          // a uniform row base plus the lane's unsigned 32-bit offset: the store's
-          // saddr form, no 64-bit VALU address per step (the offset is named in
-          // the step, or its 64-bit extension is hoisted out of the loop and the
-          // add of the row base comes back)
-          if constexpr (RP && TSA_RING_ST_SADDR) asm volatile("" : "+v"(own));
-          uint4 *dst = (uint4 *)__builtin_assume_aligned(
-              RP && TSA_RING_ST_SADDR ? (ring + (int64_t)st_row * SLOT_BYTES) + own
-                                      : ring + (int64_t)st_row * SLOT_BYTES + lane * REC_BYTES,
-              16);
+        // RP: a uniform row base plus the lane's unsigned 32-bit offset, which the
+        // compiler selects as the store's saddr form, no 64-bit VALU address per
+        // step (the offset is named in the step, or its 64-bit extension is
+        // hoisted out of the loop and the add of the row base comes back)
+        if constexpr (RP) asm volatile("" : "+v"(own));
+        uint4 *dst = (uint4 *)__builtin_assume_aligned(
+            RP ? (ring + (int64_t)st_row * SLOT_BYTES) + own : ring + (int64_t)st_row * SLOT_BYTES + lane * REC_BYTES,
+            16);
 #pragma unroll
-          for (int i = 0; i < M; ++i) {
-            if constexpr (TSA_RING_NT & 1) {
-              typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-              const u32x4 v = {oIy[i], oIxy[i], oIyz[i], oBest[i]};
-              __builtin_nontemporal_store(v, (u32x4 *)(dst + i * 64));
-            } else {
-              dst[i * 64] = make_uint4(oIy[i], oIxy[i], oIyz[i], oBest[i]);
-            }
-          }
-        } else {  // shifted, as the LDS records above, through buffer stores: the ring
-          // an SGPR resource, the row in soffset, the lane's place a loop-invariant VGPR
-          // (constant offsets ride in soffset: the compiler does not fold them
-          // into a buffer store's immediate, and a VGPR each would cost occupancy)
-          const int32_t row = st_row * SLOT_BYTES;
-#pragma unroll
-          for (int i = 0; i < M; ++i) {
-            ring_st64(rs_ring, own, row + i * PAIR_BYTES, oIy[i], oIxy[i]);
-            if (i + 1 < M) ring_st64(rs_ring, own, row + (i + 1) * PAIR_BYTES + 8, oIyz[i], oBest[i]);
-          }
-          if (lane < 63) {
-            ring_st64(rs_ring, own, row + REC_BYTES + 8, oIyz[M - 1], oBest[M - 1]);
-          } else if constexpr (!TWO) {  // lane 63 -> lane 0's high halves: the resource 63 records lower
-            ring_st16(rs_ring63, own, row + 10, oIyz[M - 1]);
-            ring_st16(rs_ring63, own, row + 14, oBest[M - 1]);
-          }
-        }
+        for (int i = 0; i < M; ++i) dst[i * 64] = make_uint4(oIy[i], oIxy[i], oIyz[i], oBest[i]);
       }
       // ---- END: fold this step's real cells into the positions' keys. Position k
       // holds x - 1 = xpos0 - k of row lap0 NW + w + 1 once it has wrapped
@@ -1171,11 +859,10 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
 #pragma unroll
       for (int i = 0; i < M; ++i) { rz[i] = rec[i].z; rw[i] = rec[i].w; }
       // position 0 advances to u0 + 1
-      // (TSA_EV_STATIC: the events fall on step (2w - 1) mod 4 of a group only)
-      constexpr bool EV_SKIP = VS && M == 2 && TSA_EV_STATIC && HSK == 2 && WPAR >= 0 && PQ >= 0 && PQ < 4 &&
+      // (V-space M = 2, P a multiple of 4: the events fall on step (2w - 1) mod 4 of a group only)
+      constexpr bool EV_SKIP = VS && M == 2 && HSK == 2 && WPAR >= 0 && PQ >= 0 && PQ < 4 &&
                                (PQ & 3) != (WPAR == 0 ? 3 : 1);
       auto advance = [&]() {
-#if TSA_HM_TRACK
         if constexpr (EV_SKIP) {
           ++xpos0;
           return;
@@ -1187,39 +874,17 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
             row_terms();
             if constexpr (VS) {  // a new row at position 0: H(t .. t+2) restart
               const int32_t y = lap0 * NW + w + 1;
-              if constexpr (HT) {
-                // and what was fetched for the steps after this one restarts too
-                const int32_t q1 = pa.lam * (y + 1);
-                Hr[PQ & 3] = h_tab(q1 - 2 * pa.lam);
-                Hr[(PQ + 1) & 3] = h_tab(q1 - pa.lam);
-                Hr[(PQ + 2) & 3] = h_tab(q1);
-#pragma unroll
-                for (int j = (PQ & 3) + 1; j < 4; ++j) Hn[j] = h_tab(q1 + (j - (PQ & 3)) * pa.lam);
-                hg = q1 + (3 - (PQ & 3)) * pa.lam;
-                if constexpr ((PQ & 3) >= 2) h_tab4(std::bool_constant<L1>{}, hg + pa.lam, Hp);  // already fetched (step 2)
-              } else {
-                Hr[PQ & 3] = h_bits(pa.lam * (y - 1));
-                Hr[(PQ + 1) & 3] = h_bits(pa.lam * y);
-                Hr[(PQ + 2) & 3] = h_bits(pa.lam * (y + 1));
-              }
+              Hr[PQ & 3] = h_bits(pa.lam * (y - 1));
+              Hr[(PQ + 1) & 3] = h_bits(pa.lam * y);
+              Hr[(PQ + 2) & 3] = h_bits(pa.lam * (y + 1));
             }
           }
           hmCur = hm_of(xpos0);
           next_ev = ev_of(xpos0);
         }
-#else
-        static_assert(!VS, "V-space tracks the lap wrap with the half-mask events");
-        if (++xpos0 == P) {
-          xpos0 = 0;
-          binj = b_of_lap(++lap0);
-          row_terms();
-        }
-#endif
       };
       if constexpr (VS) {
-        if constexpr (HT) {
-          Hr[(PQ + 2) & 3] = Hn[PQ & 3];
-        } else if constexpr (VI) {
+        if constexpr (VI) {
           Hr[(PQ + 2) & 3] = Hr[(PQ + 1) & 3] + pa.i_lam;
         } else {
           Hr[(PQ + 2) & 3] = U(H(Hr[(PQ + 1) & 3]) + H(pa.v_lam));
@@ -1227,47 +892,9 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
         advance();
         // z = 0 faces of position 0: (x, y, 0) and (x, y-1, 0) at step t+1,
         // (x-1, y, 0) and (x-1, y-1, 0) at step t+2
-        if constexpr (TSA_ABL_ZOWN) {
-          zmove_abl<M>(shIxz[PH], oIxz);
-          zmove_abl<M>(shIz, oIz);
-        } else {
-          zshift<M>(shIxz[PH], oIxz, sel, Hr[(PQ + 2) & 3]);
-          zshift<M>(shIz, oIz, sel, Hr[(PQ + 1) & 3]);
-        }
-        if constexpr (SHR) {  // the writer shifted them (TSA_SHIFTED_REC)
-#pragma unroll
-          for (int i = 0; i < M; ++i) {
-            svIyz[i] = rz[i];
-            svM[PH][i] = rw[i];
-          }
-          // lane 0's pair-0 {Iyz, best} low halves: the z = 0 face of the reader's
-          // position 0 (TWO: both halves), once the lap-wrap update has set it
-          const uint32_t face = Hr[(PQ + 2) & 3];
-          if (lane == 0) {
-            if constexpr (ROLE != 2) {
-              lds_u8 *f0 = wr_base + (HSK == 2 ? q : PH) * SLOT_BYTES;
-              if constexpr (TWO) {
-                lds_w32_at(f0, 8, face);
-                lds_w32_at(f0, 12, face);
-              } else {
-                lds_w16_at(f0, 8, face);
-                lds_w16_at(f0, 12, face);
-              }
-            } else {
-              const int32_t row = st_row * SLOT_BYTES;
-              if constexpr (TWO) {
-                ring_st32(rs_ring, own, row + 8, face);
-                ring_st32(rs_ring, own, row + 12, face);
-              } else {
-                ring_st16(rs_ring, own, row + 8, face);
-                ring_st16(rs_ring, own, row + 12, face);
-              }
-            }
-          }
-        } else if constexpr (TSA_ABL_ZREC) {
-          zmove_abl<M>(svIyz, rz);
-          zmove_abl<M>(svM[PH], rw);
-        } else if constexpr (RP && ROLE == 3) {  // every position holds the face itself, H(t + 1)
+        zshift<M>(shIxz[PH], oIxz, sel, Hr[(PQ + 2) & 3]);
+        zshift<M>(shIz, oIz, sel, Hr[(PQ + 1) & 3]);
+        if constexpr (RP && ROLE == 3) {  // every position holds the face itself, H(t + 1)
 #pragma unroll
           for (int i = 0; i < M; ++i) {
             svIyz[i] = rz[i];
@@ -1280,7 +907,6 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
           zshift<M>(svIyz, rz, sel, Hr[(PQ + 1) & 3]);
           zshift<M>(svM[PH], rw, sel, Hr[(PQ + 1) & 3]);
         }
-        if constexpr (PRE) vs_inject(std::integral_constant<int, (PQ + 1) & 3>{});  // the next step's x = 1
       } else {
         zshift<M>(shIxz[PH], oIxz, sel, pa.f_pair);  // z = 0 face for position 0
         zshift<M>(shIz, oIz, sel, pa.f_single);
@@ -1303,12 +929,12 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
             load_a_off<M>(abase, (PQ & 3) + 2, a_ev);
           }
         }
-      } else if constexpr (TSA_A_PREFETCH) {
+      } else {
         load_a<M>(a_lane + 4u * (uint32_t)xpos0, a_nx);
       }
 
       // ---- wave 0: fetch the record of step t + PD into the slot just consumed
-      if constexpr (ISS_AT) {  // SF: the row of step t + 6 + iss_j, into that step's slot
+      if constexpr (ISS_AT) {  // the row of step t + 6 + iss_j, into that step's slot
         const uint32_t slot = ((uint32_t)t * SLOT_BYTES + iss_slot0) & (uint32_t)(PD * SLOT_BYTES - 1);
         dma16x2_saddr(ring + (int64_t)dma_row * SLOT_BYTES, dvo0, dvo1, xr0_lds + slot, xr0_lds + slot + PAIR_BYTES);
         dma_row += 2;
@@ -1316,37 +942,26 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
       }
       // the two rows issued after the one now due stay in flight (M loads a row)
       if constexpr (ISS_WAIT) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * M) : "memory");
-      if constexpr (ROLE == 0 && !SF && TSA_ABL_RING != 1 && TSA_ABL_RING != 3) {
+      if constexpr (ROLE == 0 && !RP) {
 #pragma unroll
         for (int i = 0; i < M; ++i)
-          if constexpr (TSA_DMA_SADDR && M == 2) {
+          if constexpr (M == 2) {  // the row's two pieces in one statement
             if (i == 0)
               dma16x2_saddr(ring + (int64_t)dma_row * SLOT_BYTES, dvo0, dvo1,
                             xr0_lds + (uint32_t)((t % PD) * SLOT_BYTES),
                             xr0_lds + (uint32_t)((t % PD) * SLOT_BYTES + PAIR_BYTES));
-          } else if constexpr (TSA_RING_NT & 2)
-            dma16_nt(ring + ((int64_t)dma_row * M + i) * PAIR_BYTES + lane * REC_BYTES,
-                     xr0 + (t % PD) * SLOT_BYTES + i * PAIR_BYTES);
-          else
+          } else
             dma16(ring + ((int64_t)dma_row * M + i) * PAIR_BYTES + lane * REC_BYTES,
                   xr0 + (t % PD) * SLOT_BYTES + i * PAIR_BYTES);
         if (++dma_row == R) dma_row = 0;
       }
       if constexpr (ROLE == 2) {
         if (++st_row == R) st_row = 0;
-        // stores per step: M records, or SHR's 2M + 4 (TWO: 2M + 2) pieces
-        // (lane 0's two face stores included)
-        constexpr int NST = SHR ? 2 * M + (TWO ? 2 : 4) : M;
-        constexpr int VMW = NST * STORE_SLACK < 63 ? NST * STORE_SLACK : 63;  // 6-bit vmcnt
+        constexpr int VMW = M * STORE_SLACK < 63 ? M * STORE_SLACK : 63;  // M stores per step; 6-bit vmcnt
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VMW) : "memory");
       }
       // skew 2: a wave reads records two steps old, so one barrier per pair of steps
-      // (HT: the group's last barrier names the fetched H values, so the wait
-      // the compiler owes them stands here, where lgkmcnt(0) is waited for anyway)
-      if constexpr (HT && PQ == 3)
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier"
-                     : "+s"(Hp[0]), "+s"(Hp[1]), "+s"(Hp[2]), "+s"(Hp[3])::"memory");
-      else if constexpr (HSK == 1 || PH == 1) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      if constexpr (HSK == 1 || PH == 1) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     };
 
     // the last step is peeled off (it records the final cell), so the loop
@@ -1364,17 +979,9 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
       constexpr std::false_type mid{};
       constexpr std::true_type last{};
       if constexpr (VS) {  // whole groups of four steps (H's phase is t & 3), the final cell tested
-        // SHR: lane 63's write base in a VGPR (uniform, the compiler would keep it
-        // in an SGPR and copy it into a VGPR before every write)
-        if constexpr (SHR) asm volatile("" : "+v"(wrH));
         auto group_bases = [&]() {  // the A addresses of the group's first step
           abase = a_lane + 4u * (uint32_t)xpos0;
           if constexpr (A_B64) abase_s = a_lane_s + 4u * (uint32_t)xpos0;
-          if constexpr (HT) {  // the values fetched in the last group become this one's
-            hg += 4 * pa.lam;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) Hn[j] = Hp[j];
-          }
           if constexpr (RP && (decltype(role)::value & 3) == 0) {  // wave 0: slots (t & 4) .. + 3 (t % 4 == 0)
             r0_own = rd_base + (t & 4) * SLOT_BYTES;
             r0_prev = rd_prev + (t & 4) * SLOT_BYTES;
@@ -1392,19 +999,19 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
             TSA_INLINE_IF_WIDE(step(Q2, first, t + 2, mid));
             TSA_INLINE_IF_WIDE(step(Q3, first, t + 3, mid));
           }
-          if constexpr (!SF) {
+          if constexpr (!RP) {
             if (t < T) prime(t);
           }
         }
 #pragma unroll 1
-        for (; t < (SF && (decltype(role)::value & 3) == 1 ? min(t_iss, T) : T); t += 4) {
+        for (; t < (RP && (decltype(role)::value & 3) == 1 ? min(t_iss, T) : T); t += 4) {
           group_bases();
           TSA_INLINE_IF_WIDE(step(Q0, role, t, mid));
           TSA_INLINE_IF_WIDE(step(Q1, role, t + 1, mid));
           TSA_INLINE_IF_WIDE(step(Q2, role, t + 2, mid));
           TSA_INLINE_IF_WIDE(step(Q3, role, t + 3, mid));
         }
-        if constexpr (SF && (decltype(role)::value & 3) == 1) {
+        if constexpr (RP && (decltype(role)::value & 3) == 1) {
           // the issuers' groups from t_iss on: the same steps with the fetch
           // statements (a middle wave that issues nothing has left the loop above at T)
           constexpr std::integral_constant<int, decltype(role)::value | 32> issuing{};
@@ -1419,15 +1026,13 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
         }
         return;
       }
-#if TSA_UNROLL4
 #pragma unroll 1
-      for (; (M <= 2 || HSK == 2) && t + 3 < T1; t += 4) {
+      for (; (M <= 2 || HSK == 2) && t + 3 < T1; t += 4) {  // four steps a body where the step is small
         TSA_INLINE_IF_WIDE(step(Q0, role, t, mid));
         TSA_INLINE_IF_WIDE(step(Q1, role, t + 1, mid));
         TSA_INLINE_IF_WIDE(step(Q2, role, t + 2, mid));
         TSA_INLINE_IF_WIDE(step(Q3, role, t + 3, mid));
       }
-#endif
 #pragma unroll 1
       for (; t + 1 < T1; t += 2) {
         TSA_INLINE_IF_WIDE(step(P0, role, t, mid));
@@ -1441,24 +1046,12 @@ __global__ __launch_bounds__(64 * NW) void pencil_kernel(const uint8_t *__restri
       }
     };
     // role | (w & 1) + 1 << 2 (M = 2, see ISC in step)
-    constexpr int W0 = (M == 2 && TSA_IS_STATIC) ? 4 : 0, W1 = (M == 2 && TSA_IS_STATIC) ? 8 : 0;
+    constexpr int W0 = M == 2 ? 4 : 0, W1 = M == 2 ? 8 : 0;
     static_assert(NW % 2 == 0, "the last wave is odd");
-    if constexpr (PRE) vs_inject(std::integral_constant<int, 0>{});  // step 0's x = 1
-    // (bit 4, HT: the loop's version for lam = 1, whose four H values of a group
-    // are one four-dword load)
-    auto run_wave = [&](auto l1) {
-      constexpr int LB = decltype(l1)::value ? 16 : 0;
-      if (w == 0) TSA_INLINE_IF_WIDE(run(std::integral_constant<int, 0 + W0 + LB>{}));
-      else if (w == NW - 1) TSA_INLINE_IF_WIDE(run(std::integral_constant<int, 2 + W1 + LB>{}));
-      else if (W0 != 0 && (w & 1)) TSA_INLINE_IF_WIDE(run(std::integral_constant<int, 1 + W1 + LB>{}));
-      else TSA_INLINE_IF_WIDE(run(std::integral_constant<int, 1 + W0 + LB>{}));
-    };
-    if constexpr (HT) {
-      if (pa.lam == 1) run_wave(std::true_type{});
-      else run_wave(std::false_type{});
-    } else {
-      TSA_INLINE_IF_WIDE(run_wave(std::false_type{}));
-    }
+    if (w == 0) TSA_INLINE_IF_WIDE(run(std::integral_constant<int, 0 + W0>{}));
+    else if (w == NW - 1) TSA_INLINE_IF_WIDE(run(std::integral_constant<int, 2 + W1>{}));
+    else if (W0 != 0 && (w & 1)) TSA_INLINE_IF_WIDE(run(std::integral_constant<int, 1 + W1>{}));
+    else TSA_INLINE_IF_WIDE(run(std::integral_constant<int, 1 + W0>{}));
     if constexpr (END) {
       // z and the wave's row join the key here: {score | ~(x-1)} : ~y : ~z, so the
       // largest is the best score at the smallest x, then y, then z. Positions
@@ -1639,7 +1232,7 @@ static bool use_vs(const KParams &kp, const Range &r, int32_t max_la, int32_t ma
 
 // The integer-pattern V-space cell (cell_messages_vi), consulted only where
 // use_vs holds: the bias, or 0 where the float cell stays. Restricted to the
-// case TSA_REC_PREV is restricted to (M = 2, not TWO, skew 2). Every half of a
+// RP forms of the kernel (M = 2, not TWO, skew 2). Every half of a
 // started position must stay inside [0x0400, 0x7BFF] (a carry out of a low half
 // would reach a live high half), padding and run-on cells included. Those are
 // cells too: a padding symbol's code is 0, which matches nothing, so the
@@ -1655,18 +1248,12 @@ static bool use_vs(const KParams &kp, const Range &r, int32_t max_la, int32_t ma
 // sum) lie under the upper end. Widened by pencil_slack for the - 8 CP, - 8 LAM
 // and bonus intermediates, scaled by 8, the interval must fit the window.
 // pencil_arith = f16vf keeps the float cell; f16vi is refused where this is 0.
-#ifndef TSA_VI_DEFAULT  // the integer cell wherever it is admitted (0: only under f16vi)
-#define TSA_VI_DEFAULT 1
-#endif
+// The integer cell runs wherever it is admitted.
 constexpr int32_t VI_LO = 0x0400, VI_HI = 0x7BFF;
-// the build's switches leave the form the integer cell is written for (else it is not instantiated)
-constexpr bool VI_BUILT = TSA_REC_PREV && !TSA_H_TAB && !TSA_SHIFTED_REC && !TSA_PREINJ && TSA_SKEW == 2 &&
-                          PENCIL_NW == 8;
 static int32_t use_vi(const KParams &kp, const Range &r, int32_t max_la, int32_t max_lb, int32_t max_lc) {
   if (arith_override("f16vf") || !use_vs(kp, r, max_la, max_lb, max_lc)) return 0;
-  if (!TSA_VI_DEFAULT && !arith_override("f16vi")) return 0;
   const PencilGeom g = pencil_geom(max_la, max_lc);
-  if (!VI_BUILT || g.M != 2 || g.two) return 0;
+  if (g.M != 2 || g.two) return 0;
   const int32_t GE = kp.pen[SIXY][SIX], GO = kp.pen[SIXY][SM];
   const int64_t e_la = g.P, e_lb = (int64_t)max_lb + 2 * helix_nw(g.M), e_lc = 128 * g.M;
   const int64_t mn = std::min<int64_t>(max_la, std::min(max_lb, max_lc)), e_mn = std::min(e_la, std::min(e_lb, e_lc));
@@ -1711,7 +1298,7 @@ static int launch_m(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n,
   const bool two = M == 1 && g.two;
   auto kfn = vs ? (two ? pencil_kernel<M, NW, F16, SOP, M == 1, VSOK> : pencil_kernel<M, NW, F16, SOP, false, VSOK>)
                 : (two ? pencil_kernel<M, NW, F16, SOP, M == 1, false> : pencil_kernel<M, NW, F16, SOP, false, false>);
-  if constexpr (VSOK && M == 2 && VI_BUILT) {  // the integer-pattern cell (use_vi set the bias)
+  if constexpr (VSOK && M == 2) {  // the integer-pattern cell (use_vi set the bias)
     if (vs && pa.bias != 0) kfn = pencil_kernel<M, NW, F16, SOP, false, VSOK, true>;
   }
   if (d_ends) {
@@ -1719,7 +1306,7 @@ static int launch_m(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n,
       if (two) return TSA_EINVAL;
       kfn = vs ? pencil_kernel<M, NW, F16, SOP, false, VSOK, false, true>
                : pencil_kernel<M, NW, F16, SOP, false, false, false, true>;
-      if constexpr (M == 2 && VI_BUILT) {
+      if constexpr (M == 2) {
         if (vs && pa.bias != 0) kfn = pencil_kernel<M, NW, F16, SOP, false, VSOK, true, true>;
       }
     } else {
@@ -1838,8 +1425,6 @@ int pencil_launch_batch(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t
   const PencilGeom g = pencil_geom(max_la, max_lc);
   const int32_t grid = n < 65535 ? n : 65535;
   if (ws_bytes < (size_t)grid * (size_t)g.ring_bytes_per_triple) return TSA_ENOMEM;
-  if (PENCIL_NW != 8 && g.M == 2 && f16 && !sop)
-    return launch_m<2, PENCIL_NW, true, false>(d_seqs, d_offsets, n, max_lb, g, d_scores, d_ws, pa, stream);
   return TSA_SHAPES(launch_m, g.M, f16, sop, d_seqs, d_offsets, n, max_lb, g,
                     d_scores, d_ws, pa, stream);
 }

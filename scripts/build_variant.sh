@@ -4,7 +4,7 @@
 # The diagnostic knobs (TSA_LAP_SINGLE, TSA_LAP_RING_SLACK, TSA_LAP_FULL_RINGS,
 # per-phase cycle counters) exist only in a -DTSA_DIAG build:
 #   scripts/build_variant.sh diag "-DTSA_DIAG"
-#   scripts/build_variant.sh nopf "-DTSA_A_PREFETCH=0"
+#   scripts/build_variant.sh nostatic "-DTSA_LIT_STATIC=0"
 set -e
 cd "$(dirname "$0")/.."
 NAME=$1; DEFS=$2

@@ -123,7 +123,7 @@ def test_describe_plan(tsa):
     assert tsa.get_overrides() == {}
     # M = 2 lap periods are multiples of 4: even (the x = 1 register is then
     # PH ^ (w & 1)), and each wave's lap-wrap events fall on one static step of
-    # the four-step group (TSA_EV_STATIC)
+    # the four-step group (EV_SKIP in csrc/pencil_kernel.hip)
     assert "M=2 NW=8 P=260" in tsa.describe_plan(512, 257, 40, 255, p)
     assert "M=2 NW=8 P=256" in tsa.describe_plan(512, 255, 40, 255, p)
     p16 = tsa.TsaParams.default(score_bits=16)

@@ -1,8 +1,8 @@
 """The V-space M = 2 helix with the row above's {Iyz, best} read at position
-k - 1 (TSA_REC_PREV in csrc/pencil_kernel.hip), bit-exact against the C oracle.
-The same cases hold for the form that is built but off by default, the face
-values read from the constant table (TSA_H_TAB: the table's stride and its
-saturated tail below); a build with that switch set runs this file unchanged.
+k - 1 (the RP forms of csrc/pencil_kernel.hip), bit-exact against the C oracle.
+The lam > 1 and lam q > 2047 cases below were written when the kernel also had
+a form that read the face values from a constant table with a saturated tail
+(DESIGN.md 4.2); they exercise the kernel's f16 and integer face values as well.
 
 Every batch is three ragged triples (the first at the full lengths) on a
 workspace poisoned with f16 +inf, as tests/test_helix_ring_rows.py does: with
@@ -17,17 +17,15 @@ Shapes (small: 256 x 17 x 256 is 1.1 M cells):
     four-step group, three laps, so wave 0 reads shifted from the ring rows;
   * LB = 1, 8 (no second lap) and 9 (the first row that comes through the ring);
   * the largest LB the V-space plan accepts at a short A, for every admitted
-    lam (1..6): lam q passes 2047 at padding positions only, and the table's
-    saturated tail is read by TSA_H_TAB; the default form's f16 adds pass 2047
-    there.
+    lam (1..6): lam q passes 2047 at padding positions only, where the face
+    values' f16 adds pass 2047 too.
 Parameters: both s3 modes, and every lam = GE = -mismatch the V-space plan
 admits at each shape, with gap_open = lam + 1 and the match that keeps
 match - mismatch at 2 (at 1 where only that is admitted: the f16 forms bound
 the score deltas): lam = 1..6 at LC = 129, 130 and at the LB = 1, 8, 9 shapes,
 1..5 at LC = 255, 256, 1..3 at the lap-wrap shapes. test_lam_lists_are_complete
 asks the plan for lam = 1..9 at every shape and fails if a list above leaves an
-admitted lam out. With TSA_H_TAB, lam > 1 reads the table at that stride, one
-load per value."""
+admitted lam out."""
 import sys
 
 import numpy as np
@@ -141,8 +139,8 @@ def test_lam_lists_are_complete(gpu, orc):
 def test_table_tail_at_padding_positions(gpu, orc, lam):
     """LA = 2, LC = 129 and the largest LB the V-space plan accepts for lam, over
     the candidate parameter sets: P = 256, so position 0 of the last rows runs
-    through padding columns up to x = 256, where lam (y + x) passes 2047 -- with
-    TSA_H_TAB the index is clamped into the table's saturated tail. Those cells
+    through padding columns up to x = 256, where lam (y + x) passes 2047, the
+    last integer step the f16 face values take exactly. Those cells
     feed padding cells only. (No LB is admitted for lam = 7 and up.)"""
     sys.modules["tsa_amd"].set_override("TSA_PENCIL_MODE", "helix")
 

@@ -1,4 +1,4 @@
-"""The helix's row-above z-shift by read address (TSA_REC_PREV in
+"""The helix's row-above z-shift by read address (the RP forms of
 csrc/pencil_kernel.hip) on the CPU: tools/pencil_emu.py with read_prev=True
 takes {Iyz, best} of the row above from the record of position k-1 -- register
 i-1 of the lane, register M-1 of lane-1, lane 63 for lane 0 -- and fixes only

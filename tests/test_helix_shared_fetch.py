@@ -1,5 +1,5 @@
-"""The helix's shared ring fetch on the GPU (csrc/pencil_kernel.hip,
-TSA_FETCH_SHARED): waves 1 and 2 issue the LDS-DMA fetches of wave 0's ring rows
+"""The helix's shared ring fetch on the GPU (csrc/pencil_kernel.hip, the RP
+forms): waves 1 and 2 issue the LDS-DMA fetches of wave 0's ring rows
 at static steps of the four-step group, wave 0 only reads its slots, and the
 step barrier is the only order between them. A fetch that lands late, or over
 a row wave 0 has not read, gives a wrong score; a row fetched before the last

@@ -1,5 +1,5 @@
-"""The helix's shared ring fetch on the CPU (csrc/pencil_kernel.hip,
-TSA_FETCH_SHARED): tools/pencil_emu.py `shared_fetch` replays which middle wave
+"""The helix's shared ring fetch on the CPU (csrc/pencil_kernel.hip, the RP
+forms): tools/pencil_emu.py `shared_fetch` replays which middle wave
 issues each of wave 0's ring rows, at which step of the four-step group, into
 which slot of wave 0's LDS copy, and when the issuer's counted wait and the
 step barrier make the row readable. A slot in flight holds garbage, the ring

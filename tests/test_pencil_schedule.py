@@ -13,8 +13,8 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 
 
 def _form(vs):
-    """vs: False (message form), True (V-space, writer-shifted records: the
-    kernel's TSA_SHIFTED_REC), "noshift" (V-space, the reader's z-shift). The
+    """vs: False (message form), True (V-space, writer-shifted records: a layout
+    the kernel no longer has), "noshift" (V-space, the reader's z-shift). The
     LDS record slots start with garbage, as on the GPU (a slot read before any
     write must not reach a real cell: the shifted form's seeded faces)."""
     return dict(vs=bool(vs), shifted=vs is True, garbage_seed=17)

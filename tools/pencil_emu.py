@@ -13,14 +13,16 @@ records of its steps before t_sw from its own H values, only the ring rows of
 steps [t_sw, lag) are filled, and `ring_garbage_seed` starts the ring as
 garbage, so a row read before it is written shows (tests/test_helix_ring_emu.py).
 
-`shifted=True` (V-space only; the kernel's TSA_SHIFTED_REC) replays the
-writer-side record shift: a wave (and the last wave, into the ring) stores
+`shifted=True` (V-space only) models a record layout the kernel no longer has
+(the writer-shifted records of DESIGN.md 4.2, retired after they measured
+slower); it stays as an independent replay of the algebra against the oracle.
+It replays the writer-side record shift: a wave (and the last wave, into the ring) stores
 each position's {Iyz, best} at position k+1, lane 0's low halves carrying the
 z = 0 face the READER needs -- the writer's own H(t+2) after its lap-wrap
 update, which equals the reader's H(t'+1) two steps later (same u, one row
 down) -- so the reader takes Iyz and M from its record with no z-shift.
 
-`read_prev=True` (V-space, not `shifted`; the kernel's TSA_REC_PREV) replays
+`read_prev=True` (V-space, not `shifted`; the kernel's RP forms) replays
 the reader-side address rule: a lane takes {Iyz, best} of the row above from
 the RECORD of position k-1 -- register i-1 of its own lane, or register M-1 of
 lane-1 (lane 63 for lane 0) for register 0 -- and only lane 0's register 0 is
@@ -57,8 +59,8 @@ messages). V-space values are shifted by lam (x + y + z). These are what
 pencil_slack (csrc/pencil_kernel.hip) has to cover around the candidate range
 (tests/test_range_proof.py). Without the key nothing is recorded.
 
-`shared_fetch=True` (V-space with `read_prev`, M = 2; the kernel's
-TSA_FETCH_SHARED) replays who fetches wave 0's ring rows and when. Wave 0 reads
+`shared_fetch=True` (V-space with `read_prev`, M = 2; the kernel's RP forms)
+replays who fetches wave 0's ring rows and when. Wave 0 reads
 step t's row from slot t mod PD of its LDS ring copy (xr0) and issues nothing;
 waves 1 and 2 issue at the first and the third step t of every four-step group,
 from PD steps before t_sw on, the row of step t + 6 (wave 1) or t + 7 (wave 2)
@@ -211,7 +213,7 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
     KS = 64 if two else 128 * M
     P = max(max_la, 64 if two else 128 * M)
     P = -(-P // M) * M
-    if M == 2 and not two:  # the kernel's TSA_EV_STATIC: P a multiple of 4
+    if M == 2 and not two:  # as the kernel's pencil_geom: P a multiple of 4
         P = -(-P // 4) * 4
     R = P + RING_EXTRA
     lam = ge if vs else 0
@@ -355,7 +357,7 @@ def emulate(triples, match=1, mismatch=-1, go=2, ge=1, sop=False, vs=False, shif
         return out
 
     def prev_read(v, face):
-        # TSA_REC_PREV: each (lane, register) reads the record of position k-1 by
+        # read_prev: each (lane, register) reads the record of position k-1 by
         # its address -- register i-1 of the lane, or register M-1 of lane-1 (mod
         # 64) -- both halves as they lie there; then lane 0's register 0 takes
         # {face, lane 63's low half} (TWO: the face in both halves)
