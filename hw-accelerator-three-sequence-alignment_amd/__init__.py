@@ -69,7 +69,7 @@ EXPORTS = (
     "tsa_align_batch_ends", "tsa_score_batch_ends", "tsa_score_ends_workspace_size",
     "tsa_score_batch_ends_async", "tsa_describe_score_ends_plan", "tsa_align_batch_grid_ends",
     "tsa_score_batch_ends_ex", "tsa_score_ends_workspace_size_ex", "tsa_score_batch_ends_async_ex",
-    "tsa_describe_score_ends_plan_ex",
+    "tsa_describe_score_ends_plan_ex", "tsa_align_ends_workspace_size", "tsa_align_batch_ends_async",
 )
 
 # Plan overrides the library accepts (tsa_set_override; include/trialign.h).
@@ -190,6 +190,10 @@ def _load_lib() -> ctypes.CDLL:
                                           ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_size_t, ctypes.c_void_p]
+    lib.tsa_align_ends_workspace_size.argtypes = [i64p, ctypes.c_int32, pp, ctypes.c_int32, ctypes.c_int32, szp, szp]
+    lib.tsa_align_batch_ends_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, i64p, ctypes.c_int32, pp,
+                                               ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 6 + \
+        [ctypes.c_size_t, ctypes.c_void_p]
     lib.tsa_align_rows_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32] + \
         [ctypes.c_void_p] * 5
     lib.tsa_score_gpu_multi.argtypes = [u8p, ctypes.c_int32, u8p, ctypes.c_int32, u8p,
@@ -219,7 +223,8 @@ def _load_lib() -> ctypes.CDLL:
                  "tsa_align_batch_async", "tsa_align_rows_async", "tsa_align_batch_ends", "tsa_score_batch_ends",
                  "tsa_score_ends_workspace_size", "tsa_score_batch_ends_async", "tsa_describe_score_ends_plan",
                  "tsa_align_batch_grid_ends", "tsa_score_batch_ends_ex", "tsa_score_ends_workspace_size_ex",
-                 "tsa_score_batch_ends_async_ex", "tsa_describe_score_ends_plan_ex"):
+                 "tsa_score_batch_ends_async_ex", "tsa_describe_score_ends_plan_ex",
+                 "tsa_align_ends_workspace_size", "tsa_align_batch_ends_async"):
         getattr(lib, name).restype = ctypes.c_int
     return lib
 
@@ -880,6 +885,86 @@ def align_batch_device(d_seqs, offsets, params: Optional[TsaParams] = None, path
                           n_moves.data_ptr(), starts.data_ptr(), workspace.data_ptr(), workspace.numel(),
                           st.cuda_stream, params, path)
         out = (scores[:n], moves[:total], n_moves[:n], starts[:3 * n])
+        if rows:
+            d_rows = _torch.full((max(3 * total, 1),), ROW_GAP, dtype=_torch.uint8, device=dev)
+            align_rows_async(d_seqs.data_ptr(), d_off.data_ptr(), n, moves.data_ptr(), n_moves.data_ptr(),
+                             starts.data_ptr(), d_rows.data_ptr(), st.cuda_stream)
+            out += (d_rows[:3 * total],)
+    return out
+
+
+def align_ends_workspace_size(offsets, params: Optional[TsaParams] = None, path: str | int = "tiled",
+                              end: str | int = "any") -> tuple:
+    """tsa_align_ends_workspace_size: ``(min_bytes, full_bytes)`` of the
+    workspace of ``align_batch_ends_async`` for the batch with these (host)
+    offsets. Host-only. ``align_workspace_size``'s under ``end="corner"`` and
+    under ``path="tiled"``; under ``path="grid"`` with a free end it adds the
+    slot offsets and one 8-byte key per tile of every over-capacity triple.
+    ``path="strip"`` with a free end raises ``TsaError(TSA_EINVAL)``."""
+    p = params or TsaParams.default()
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = (len(offsets) - 1) // 3
+    lo, hi = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(_lib.tsa_align_ends_workspace_size(_ptr(offsets, ctypes.c_int64), n, ctypes.byref(p), _align_path(path),
+                                              _end_mode(end, "align_ends_workspace_size"), ctypes.byref(lo),
+                                              ctypes.byref(hi)), "tsa_align_ends_workspace_size")
+    return int(lo.value), int(hi.value)
+
+
+def align_batch_ends_async(d_seqs_ptr: int, d_offsets_ptr: int, offsets, d_scores_ptr: int, d_moves_ptr: int,
+                           d_n_moves_ptr: int, d_starts_ptr: int, d_ends_ptr: int, d_ws_ptr: int, ws_bytes: int,
+                           stream_ptr: int = 0, params: Optional[TsaParams] = None, path: str | int = "tiled",
+                           end: str | int = "any") -> None:
+    """Device-resident end-free traceback (tsa_align_batch_ends_async):
+    ``align_batch_async`` with ``align_batch_ends``'s results -- the path ends
+    at the best cell of ``end`` ("corner", "face", "any") and ``d_ends_ptr``
+    (3n int32) receives the end cells. ``path``: "tiled" or "grid" ("strip"
+    with ``end="corner"`` only); workspace of at least
+    ``align_ends_workspace_size(...)[0]`` bytes, 256-byte aligned."""
+    p = params or TsaParams.default()
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = (len(offsets) - 1) // 3
+    rc = _lib.tsa_align_batch_ends_async(ctypes.c_void_p(d_seqs_ptr), ctypes.c_void_p(d_offsets_ptr),
+                                         _ptr(offsets, ctypes.c_int64), n, ctypes.byref(p), _align_path(path),
+                                         _end_mode(end, "align_batch_ends_async"), ctypes.c_void_p(d_scores_ptr),
+                                         ctypes.c_void_p(d_moves_ptr), ctypes.c_void_p(d_n_moves_ptr),
+                                         ctypes.c_void_p(d_starts_ptr), ctypes.c_void_p(d_ends_ptr),
+                                         ctypes.c_void_p(d_ws_ptr), ctypes.c_size_t(ws_bytes),
+                                         ctypes.c_void_p(stream_ptr))
+    _check(rc, "tsa_align_batch_ends_async")
+
+
+def align_batch_ends_device(d_seqs, offsets, params: Optional[TsaParams] = None, end: str | int = "any",
+                            path: str | int = "tiled", workspace=None, rows: bool = False, stream=None):
+    """``align_batch_ends`` for sequences that are already on the device, as
+    ``align_batch_device`` is to ``align_batch``: returns the torch tensors
+    ``(scores, moves, n_moves, starts, ends)`` -- with ``rows=True`` also the
+    gapped rows of ``align_rows_async``, which needs nothing from the end:
+    ``n_moves`` and ``starts`` define the columns -- without synchronising.
+    ``ends`` holds (x1, y1, z1) per triple; ``n_moves[i] == 0`` flags a triple
+    whose walk failed, and its ``ends`` are unspecified."""
+    import torch as _torch
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = (len(offsets) - 1) // 3
+    if not (d_seqs.is_cuda and d_seqs.dtype == _torch.uint8 and d_seqs.is_contiguous()):
+        raise TsaError(TSA_EINVAL, "d_seqs must be a contiguous CUDA uint8 tensor")
+    dev = d_seqs.device
+    st = stream if stream is not None else _torch.cuda.current_stream(dev)
+    total = int(offsets[-1] - offsets[0]) if n else 0
+    with _torch.cuda.stream(st):
+        d_off = _torch.from_numpy(offsets).to(dev)
+        scores = _torch.zeros(max(n, 1), dtype=_torch.int32, device=dev)
+        n_moves = _torch.zeros(max(n, 1), dtype=_torch.int32, device=dev)
+        starts = _torch.zeros(max(3 * n, 1), dtype=_torch.int32, device=dev)
+        ends = _torch.zeros(max(3 * n, 1), dtype=_torch.int32, device=dev)
+        moves = _torch.zeros(max(total, 1), dtype=_torch.uint8, device=dev)
+        if workspace is None:
+            workspace = _torch.empty(max(align_ends_workspace_size(offsets, params, path, end)[1], 256),
+                                     dtype=_torch.uint8, device=dev)
+        align_batch_ends_async(d_seqs.data_ptr(), d_off.data_ptr(), offsets, scores.data_ptr(), moves.data_ptr(),
+                               n_moves.data_ptr(), starts.data_ptr(), ends.data_ptr(), workspace.data_ptr(),
+                               workspace.numel(), st.cuda_stream, params, path, end)
+        out = (scores[:n], moves[:total], n_moves[:n], starts[:3 * n], ends[:3 * n])
         if rows:
             d_rows = _torch.full((max(3 * total, 1),), ROW_GAP, dtype=_torch.uint8, device=dev)
             align_rows_async(d_seqs.data_ptr(), d_off.data_ptr(), n, moves.data_ptr(), n_moves.data_ptr(),

@@ -4,8 +4,9 @@
 // the end cell as they sweep, tb_walk_ends walks from it), tsa_align_batch_grid_ends
 // (the same search by the grid kernels, a key per tile), tsa_align_gpu
 // (one triple, always the plane sweep), tsa_describe_align_plan and the
-// device-resident tsa_align_workspace_size, tsa_align_batch_async and
-// tsa_align_rows_async, which plan with the same planner against a caller's
+// device-resident tsa_align_workspace_size, tsa_align_batch_async,
+// tsa_align_ends_workspace_size, tsa_align_batch_ends_async (the free end on
+// that path) and tsa_align_rows_async, which plan with the same planner against a caller's
 // workspace and queue the same launches (helper kernels: align_async_kernel.hip). Host code
 // only: which path a triple takes, the chunks of pointer cubes, the device buffers and the
 // launches of the resident kernel (align_kernel.hip), the tiled resident kernel
@@ -408,10 +409,13 @@ inline size_t up256(size_t v) { return (v + kAlign256 - 1) & ~(kAlign256 - 1); }
 // chunk begin. Chunk [i0, i1) uses entries i0.. of every per-triple region and
 // the bytes of its triples in seqs and moves; its 3m+1 packed offsets start at
 // entry 3*i0 + (index of the chunk), so off holds 3n + (chunks <= n) entries.
+// keyed (tsa_align_batch_ends_async on the grid path with a free end): n slot
+// offsets and the `keys` end keys of the call's grid triples, one per tile; a
+// chunk uses the key region from its start. Both are empty otherwise.
 struct AlignFixed {
-  size_t seqs, moves, off, tboff, faceoff, order, scores, final7, info, walk, total;
+  size_t seqs, moves, off, tboff, faceoff, order, scores, final7, info, walk, slotoff, slots, total;
 };
-AlignFixed align_fixed_layout(int32_t n, size_t L, bool walk) {
+AlignFixed align_fixed_layout(int32_t n, size_t L, bool walk, bool keyed = false, size_t keys = 0) {
   AlignFixed f;
   size_t at = 0;
   const auto take = [&](size_t bytes) {
@@ -425,6 +429,7 @@ AlignFixed align_fixed_layout(int32_t n, size_t L, bool walk) {
   f.order = take(sizeof(int32_t) * (size_t)n), f.scores = take(sizeof(int32_t) * (size_t)n);
   f.final7 = take(sizeof(int32_t) * NSTATE * (size_t)n), f.info = take(sizeof(int32_t) * 4 * (size_t)n);
   f.walk = take(walk ? sizeof(int32_t) * ALIGN_WALK_REC * (size_t)n : 0);
+  f.slotoff = take(keyed ? sizeof(int64_t) * (size_t)n : 0), f.slots = take(keyed ? sizeof(uint64_t) * keys : 0);
   f.total = at;
   return f;
 }
@@ -437,8 +442,13 @@ struct AlignAsyncPlan {
   AlignFixed fixed;
   size_t max_need = 0, cap = SIZE_MAX;
 };
-int align_async_plan(const int64_t *h_offsets, int32_t n, const tsa_params *p, int32_t path, AlignAsyncPlan *A) {
+// end_mode = TSA_END_FACE / TSA_END_ANY (tsa_align_batch_ends_async): the plan
+// of align_batch_entry's free end -- tiled or grid, no strips -- and on the
+// grid path the key slots in the fixed part.
+int align_async_plan(const int64_t *h_offsets, int32_t n, const tsa_params *p, int32_t path, AlignAsyncPlan *A,
+                     int32_t end_mode = TSA_END_CORNER) {
   if (!h_offsets || n < 0 || !params_ok(p)) return TSA_EINVAL;
+  if (end_mode < TSA_END_CORNER || end_mode > TSA_END_ANY) return TSA_EINVAL;
   if (path != TSA_ALIGN_PATH_TILED && path != TSA_ALIGN_PATH_STRIP && path != TSA_ALIGN_PATH_GRID) return TSA_EINVAL;
   for (int32_t i = 0; i < n; ++i) {
     const int64_t *o = h_offsets + 3 * (int64_t)i;
@@ -451,6 +461,9 @@ int align_async_plan(const int64_t *h_offsets, int32_t n, const tsa_params *p, i
                                                                                                : ALIGN_MODE_TILED;
   else if (A->pl.mode != ALIGN_MODE_TILED && A->pl.mode != ALIGN_MODE_STRIP && A->pl.mode != ALIGN_MODE_GRID)
     return TSA_EINVAL;  // no resident-or-plane plan and no plane sweep on this path
+  if (end_mode != TSA_END_CORNER && (path == TSA_ALIGN_PATH_STRIP || A->pl.mode == ALIGN_MODE_STRIP))
+    return TSA_EINVAL;  // no end search on the strip path
+  A->pl.end_mode = end_mode;
   long ov = 0;
   if (override_int("align_tb_bytes", &ov)) {
     if (ov < 0) return TSA_EINVAL;
@@ -458,9 +471,76 @@ int align_async_plan(const int64_t *h_offsets, int32_t n, const tsa_params *p, i
   }
   A->T = align_plan_triples(h_offsets, n, A->pl, true);
   for (const AlignTriple &t : A->T) A->max_need = std::max(A->max_need, t.need);
+  const bool keyed = end_mode != TSA_END_CORNER && A->pl.mode == ALIGN_MODE_GRID;
+  size_t keys = 0;  // whatever the chunks: every over-capacity triple is a grid triple of its chunk
+  if (keyed)
+    for (const AlignTriple &t : A->T) keys += t.over ? (size_t)t.nty * t.ntz : 0;
   A->fixed = align_fixed_layout(n, n ? (size_t)(h_offsets[3 * (int64_t)n] - h_offsets[0]) : 0,
-                                A->pl.mode == ALIGN_MODE_STRIP || A->pl.mode == ALIGN_MODE_GRID);
+                                A->pl.mode == ALIGN_MODE_STRIP || A->pl.mode == ALIGN_MODE_GRID, keyed, keys);
   return TSA_OK;
+}
+
+// What tsa_align_workspace_size and tsa_align_ends_workspace_size return for plan A.
+int align_async_sizes(const AlignAsyncPlan &A, size_t *min_bytes, size_t *full_bytes) {
+  *min_bytes = *full_bytes = 0;
+  if (A.T.empty()) return TSA_OK;
+  // the fewest chunks: the budget bounds none (but align_tb_bytes), only the 65535 triples of a chunk do
+  std::vector<AlignChunk> chunks;
+  int rc = align_plan_chunks(A.T, A.pl, A.cap, &chunks);
+  if (rc) return rc;
+  size_t most = 0;
+  for (const AlignChunk &c : chunks) most = std::max(most, c.need);
+  *min_bytes = A.fixed.total + A.max_need;
+  *full_bytes = A.fixed.total + most;
+  return TSA_OK;
+}
+
+// tsa_align_batch_async and tsa_align_batch_ends_async (d_ends set) behind
+// their argument checks: the chunks of plan A against the workspace, launches only.
+int align_async_run(const AlignAsyncPlan &A, const uint8_t *d_seqs, const int64_t *d_offsets, const int64_t *h_offsets,
+                    const tsa_params *p, int32_t *d_scores, uint8_t *d_moves, int32_t *d_n_moves, int32_t *d_starts,
+                    int32_t *d_ends, void *d_workspace, size_t workspace_bytes, void *stream) {
+  if (tsa_device_count() <= 0) return TSA_ENODEV;
+  KParams kp;
+  int rc = build_kparams(p, &kp);
+  if (rc) return rc;
+  const bool free_end = A.pl.end_mode != TSA_END_CORNER, keyed = free_end && A.pl.mode == ALIGN_MODE_GRID;
+  if (free_end)
+    for (const AlignTriple &t : A.T)  // as align_batch_entry: far beyond any device's memory
+      if (!align_end_key_fits(t.la, t.lb, t.lc)) return TSA_ENOMEM;
+  if (workspace_bytes < A.fixed.total || workspace_bytes - A.fixed.total < A.max_need) return TSA_ENOMEM;
+  std::vector<AlignChunk> chunks;
+  if ((rc = align_plan_chunks(A.T, A.pl, std::min(workspace_bytes - A.fixed.total, A.cap), &chunks))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  uint8_t *w = (uint8_t *)d_workspace;
+  const AlignFixed &f = A.fixed;
+  (void)hipGetLastError();  // an error left over from an earlier call is not this call's
+  for (size_t k = 0; k < chunks.size(); ++k) {
+    const AlignChunk &c = chunks[k];
+    const int32_t m = c.i1 - c.i0;
+    const size_t sym0 = (size_t)(h_offsets[3 * (int64_t)c.i0] - h_offsets[0]);  // the chunk's place in seqs and moves
+    AlignChunkBufs b;
+    b.off = (int64_t *)(w + f.off) + 3 * (size_t)c.i0 + k;
+    b.tb_off = (int64_t *)(w + f.tboff) + c.i0, b.face_off = (int64_t *)(w + f.faceoff) + c.i0;
+    b.order = (int32_t *)(w + f.order) + c.i0, b.scores = (int32_t *)(w + f.scores) + c.i0;
+    b.final7 = (int32_t *)(w + f.final7) + (size_t)NSTATE * c.i0, b.info = (int32_t *)(w + f.info) + 4 * (size_t)c.i0;
+    b.seqs = w + f.seqs + sym0, b.moves = w + f.moves + sym0;
+    // the chunk's ALIGN_END_REC <= NSTATE words a triple on its part of final7; its keys from the region's start
+    b.endrec = free_end ? b.final7 : nullptr;
+    b.slot_off = keyed ? (int64_t *)(w + f.slotoff) + c.i0 : nullptr;
+    AlignDev d;
+    d.seqs = b.seqs, d.off = b.off, d.tboff = b.tb_off, d.faceoff = b.face_off;
+    d.scores = b.scores, d.final7 = b.final7, d.info = b.info, d.moves = b.moves;
+    // the faces (16-byte cells) first, then the cubes (words): c.face + c.cube = c.need bytes
+    d.faces = w + f.total, d.tb = (uint32_t *)(w + f.total + c.face), d.ws = nullptr;
+    d.walk = (int32_t *)(w + f.walk) + (size_t)ALIGN_WALK_REC * c.i0;
+    d.endrec = b.endrec, d.slots = keyed ? (uint64_t *)(w + f.slots) : nullptr, d.slotoff = b.slot_off;
+    align_launch_meta(d_offsets, c.i0, m, A.pl, b, s);
+    align_launch_pack(d_seqs, d_offsets, m, b, s);
+    if ((rc = align_queue_chunk(c, A.pl, kp, d, s))) return rc;
+    align_launch_finish(d_offsets, m, b, d_scores, d_moves, d_n_moves, d_starts, s, d_ends);
+  }
+  return hipGetLastError() == hipSuccess ? TSA_OK : TSA_EDEVICE;
 }
 }  // namespace
 
@@ -603,16 +683,16 @@ int tsa_align_workspace_size(const int64_t *h_offsets, int32_t n, const tsa_para
   AlignAsyncPlan A;
   int rc = align_async_plan(h_offsets, n, p, path, &A);
   if (rc) return rc;
-  *min_bytes = *full_bytes = 0;
-  if (n == 0) return TSA_OK;
-  // the fewest chunks: the budget bounds none (but align_tb_bytes), only the 65535 triples of a chunk do
-  std::vector<AlignChunk> chunks;
-  if ((rc = align_plan_chunks(A.T, A.pl, A.cap, &chunks))) return rc;
-  size_t most = 0;
-  for (const AlignChunk &c : chunks) most = std::max(most, c.need);
-  *min_bytes = A.fixed.total + A.max_need;
-  *full_bytes = A.fixed.total + most;
-  return TSA_OK;
+  return align_async_sizes(A, min_bytes, full_bytes);
+}
+
+int tsa_align_ends_workspace_size(const int64_t *h_offsets, int32_t n, const tsa_params *p, int32_t path,
+                                  int32_t end_mode, size_t *min_bytes, size_t *full_bytes) {
+  if (!min_bytes || !full_bytes) return TSA_EINVAL;
+  AlignAsyncPlan A;
+  int rc = align_async_plan(h_offsets, n, p, path, &A, end_mode);
+  if (rc) return rc;
+  return align_async_sizes(A, min_bytes, full_bytes);
 }
 
 int tsa_align_batch_async(const uint8_t *d_seqs, const int64_t *d_offsets, const int64_t *h_offsets, int32_t n,
@@ -624,39 +704,23 @@ int tsa_align_batch_async(const uint8_t *d_seqs, const int64_t *d_offsets, const
   int rc = align_async_plan(h_offsets, n, p, path, &A);
   if (rc) return rc;
   if (n == 0) return TSA_OK;
-  if (tsa_device_count() <= 0) return TSA_ENODEV;
-  KParams kp;
-  if ((rc = build_kparams(p, &kp))) return rc;
-  if (workspace_bytes < A.fixed.total || workspace_bytes - A.fixed.total < A.max_need) return TSA_ENOMEM;
-  std::vector<AlignChunk> chunks;
-  if ((rc = align_plan_chunks(A.T, A.pl, std::min(workspace_bytes - A.fixed.total, A.cap), &chunks))) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  uint8_t *w = (uint8_t *)d_workspace;
-  const AlignFixed &f = A.fixed;
-  (void)hipGetLastError();  // an error left over from an earlier call is not this call's
-  for (size_t k = 0; k < chunks.size(); ++k) {
-    const AlignChunk &c = chunks[k];
-    const int32_t m = c.i1 - c.i0;
-    const size_t sym0 = (size_t)(h_offsets[3 * (int64_t)c.i0] - h_offsets[0]);  // the chunk's place in seqs and moves
-    AlignChunkBufs b;
-    b.off = (int64_t *)(w + f.off) + 3 * (size_t)c.i0 + k;
-    b.tb_off = (int64_t *)(w + f.tboff) + c.i0, b.face_off = (int64_t *)(w + f.faceoff) + c.i0;
-    b.order = (int32_t *)(w + f.order) + c.i0, b.scores = (int32_t *)(w + f.scores) + c.i0;
-    b.final7 = (int32_t *)(w + f.final7) + (size_t)NSTATE * c.i0, b.info = (int32_t *)(w + f.info) + 4 * (size_t)c.i0;
-    b.seqs = w + f.seqs + sym0, b.moves = w + f.moves + sym0;
-    AlignDev d;
-    d.seqs = b.seqs, d.off = b.off, d.tboff = b.tb_off, d.faceoff = b.face_off;
-    d.scores = b.scores, d.final7 = b.final7, d.info = b.info, d.moves = b.moves;
-    // the faces (16-byte cells) first, then the cubes (words): c.face + c.cube = c.need bytes
-    d.faces = w + f.total, d.tb = (uint32_t *)(w + f.total + c.face), d.ws = nullptr;
-    d.walk = (int32_t *)(w + f.walk) + (size_t)ALIGN_WALK_REC * c.i0;
-    d.endrec = nullptr, d.slots = nullptr, d.slotoff = nullptr;  // no end-free form on this path
-    align_launch_meta(d_offsets, c.i0, m, A.pl, b, s);
-    align_launch_pack(d_seqs, d_offsets, m, b, s);
-    if ((rc = align_queue_chunk(c, A.pl, kp, d, s))) return rc;
-    align_launch_finish(d_offsets, m, b, d_scores, d_moves, d_n_moves, d_starts, s);
-  }
-  return hipGetLastError() == hipSuccess ? TSA_OK : TSA_EDEVICE;
+  return align_async_run(A, d_seqs, d_offsets, h_offsets, p, d_scores, d_moves, d_n_moves, d_starts, nullptr,
+                         d_workspace, workspace_bytes, stream);
+}
+
+int tsa_align_batch_ends_async(const uint8_t *d_seqs, const int64_t *d_offsets, const int64_t *h_offsets, int32_t n,
+                               const tsa_params *p, int32_t path, int32_t end_mode, int32_t *d_scores,
+                               uint8_t *d_moves, int32_t *d_n_moves, int32_t *d_starts, int32_t *d_ends,
+                               void *d_workspace, size_t workspace_bytes, void *stream) {
+  if (!d_seqs || !d_offsets || !d_scores || !d_moves || !d_n_moves || !d_starts || !d_ends || !d_workspace)
+    return TSA_EINVAL;
+  if ((uintptr_t)d_workspace % kAlign256) return TSA_EINVAL;
+  AlignAsyncPlan A;
+  int rc = align_async_plan(h_offsets, n, p, path, &A, end_mode);
+  if (rc) return rc;
+  if (n == 0) return TSA_OK;
+  return align_async_run(A, d_seqs, d_offsets, h_offsets, p, d_scores, d_moves, d_n_moves, d_starts, d_ends,
+                         d_workspace, workspace_bytes, stream);
 }
 
 int tsa_align_rows_async(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, const uint8_t *d_moves,

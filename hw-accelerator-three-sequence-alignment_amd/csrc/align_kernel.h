@@ -274,8 +274,8 @@ __host__ __device__ inline AlignNeed align_need(const AlignPlan &pl, int32_t la,
   return t;
 }
 
-// ---- the helper kernels of tsa_align_batch_async and tsa_align_rows_async
-// (align_async_kernel.hip). None is counted by tsa_kernel_launch_count. ------
+// ---- the helper kernels of tsa_align_batch_async, tsa_align_batch_ends_async
+// and tsa_align_rows_async (align_async_kernel.hip). None is counted by tsa_kernel_launch_count. ------
 // The buffers of one chunk of m triples, caller's triples [i0, i0 + m), in
 // launch order: the resident triples first, then the over-capacity ones, each
 // group in the caller's order. What align_run builds on the host for the
@@ -290,10 +290,14 @@ struct AlignChunkBufs {
   int32_t *info;      // 4m {moves, x0, y0, z0}, zeroed by the meta kernel
   uint8_t *seqs;      // the packed sequences
   uint8_t *moves;     // the moves, laid out as seqs
+  // tsa_align_batch_ends_async alone, null elsewhere:
+  int64_t *slot_off;  // m key offsets of the grid triples' slots, an exclusive scan (grid path with a free end)
+  int32_t *endrec;    // 5m end records (TSA_END_FACE, TSA_END_ANY); they lie on final7, as in align_run
 };
 // One workgroup: reads d_offsets[3*i0 .. 3*(i0+m)] and fills off, tb_off,
 // face_off and order of the chunk under plan pl (align_need of every triple),
-// and zeroes info.
+// and zeroes info. With b.slot_off set (the grid path with a free end) it fills
+// that as well: nty*ntz keys per over-capacity triple, 0 for a resident one.
 void align_launch_meta(const int64_t *d_offsets, int32_t i0, int32_t m, const AlignPlan &pl, const AlignChunkBufs &b,
                        hipStream_t stream);
 // One workgroup per triple: copies its la+lb+lc symbols from the caller's
@@ -302,9 +306,13 @@ void align_launch_pack(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t 
                        hipStream_t stream);
 // One workgroup per triple: score, n_moves (0 unless 1 <= moves <= la+lb+lc)
 // and start to the caller's index, and exactly n_moves bytes of moves to the
-// caller's slot d_moves + d_offsets[3i] - d_offsets[0].
+// caller's slot d_moves + d_offsets[3i] - d_offsets[0]. With d_ends set
+// (tsa_align_batch_ends_async) the END form: also d_ends[3i..3i+2], the cell of
+// the triple's end record b.endrec[5j ..], or its lengths when b.endrec is null
+// (TSA_END_CORNER).
 void align_launch_finish(const int64_t *d_offsets, int32_t m, const AlignChunkBufs &b, int32_t *d_scores,
-                         uint8_t *d_moves, int32_t *d_n_moves, int32_t *d_starts, hipStream_t stream);
+                         uint8_t *d_moves, int32_t *d_n_moves, int32_t *d_starts, hipStream_t stream,
+                         int32_t *d_ends = nullptr);
 // The gapped rows of n alignments, one wave per triple (tsa_align_rows_async).
 void align_launch_rows(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, const uint8_t *d_moves,
                        const int32_t *d_n_moves, const int32_t *d_starts, uint8_t *d_rows, hipStream_t stream);

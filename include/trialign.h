@@ -352,11 +352,11 @@ int tsa_align_batch_grid(const uint8_t *seqs, const int64_t *offsets, int32_t n,
  * chunk queues its counted launches under align_mode = tiled:
  * [resident] + [tiled].
  *
- * Not covered: the strip and grid paths, the plane sweep, tsa_align_gpu, a
- * device-resident form (tsa_align_rows_async works on uploaded results as it
- * is). A free end on the grid path, for cubes whose pointers do not fit the
- * budget, is tsa_align_batch_grid_ends below. The end-free score without a
- * path is tsa_score_batch_ends below; the prefixes it returns can be aligned on
+ * Not covered: the strip and grid paths, the plane sweep, tsa_align_gpu. A
+ * free end on the grid path, for cubes whose pointers do not fit the budget,
+ * is tsa_align_batch_grid_ends below; the device-resident form of both is
+ * tsa_align_batch_ends_async. The end-free score without a path is
+ * tsa_score_batch_ends below; the prefixes it returns can be aligned on
  * every traceback path. */
 #define TSA_END_CORNER 0
 #define TSA_END_FACE 1
@@ -395,8 +395,9 @@ int tsa_align_batch_ends(const uint8_t *seqs, const int64_t *offsets, int32_t n,
  * worst case, whatever tile the path ends in; a workgroup whose triple's path
  * has ended leaves before its first barrier.
  *
- * Not covered: the strip path, the plane sweep, tsa_align_gpu and a
- * device-resident form (tsa_align_batch_async ends at the corner). */
+ * Not covered: the strip path, the plane sweep and tsa_align_gpu. The
+ * device-resident form is tsa_align_batch_ends_async
+ * (TSA_ALIGN_PATH_GRID). */
 int tsa_align_batch_grid_ends(const uint8_t *seqs, const int64_t *offsets, int32_t n,
                               const tsa_params *p, int32_t end_mode, int32_t *scores,
                               uint8_t *moves, int32_t *n_moves, int32_t *starts,
@@ -408,7 +409,9 @@ int tsa_align_batch_grid_ends(const uint8_t *seqs, const int64_t *offsets, int32
  * helix scorer as it sweeps, with no memory per cell. The recurrence is
  * causal, so the free-end alignment is the corner alignment of the prefixes
  * a[0..x1), b[0..y1), c[0..z1): screen a batch here, then trace back only the
- * hits with any traceback entry point (tsa_align_batch, _grid, _async ...).
+ * hits with any traceback entry point (tsa_align_batch, _grid, _async ...),
+ * or trace the batch back with its free end, without leaving the device, by
+ * tsa_align_batch_ends_async.
  *
  * Layouts, validation order and thread safety are tsa_score_batch's and
  * tsa_score_batch_async's (on the async call the symbols are the caller's job,
@@ -583,10 +586,64 @@ int tsa_align_batch_async(const uint8_t *d_seqs, const int64_t *d_offsets,
                           int32_t *d_n_moves, int32_t *d_starts,
                           void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* Device-resident end-free traceback: tsa_align_batch_ends and
+ * tsa_align_batch_grid_ends under tsa_align_batch_async's calling convention.
+ * Two contracts joined:
+ *  - the results -- d_scores, d_ends (3n: the end cell x1,y1,z1), d_starts,
+ *    d_moves, d_n_moves -- are tsa_align_batch_ends's (tsa_align_batch_grid_ends's
+ *    under TSA_ALIGN_PATH_GRID; the two agree) for every triple, parameter set
+ *    and end_mode, move for move: the same candidates, MAX7 over the literal
+ *    wrapped states, ties to the smallest x, then y, then z, then the lowest
+ *    state;
+ *  - pointers, h_offsets, stream, output layout, thread safety and the promise
+ *    to only queue launches -- no allocation, no host copy, no free-memory
+ *    query, no synchronisation -- are tsa_align_batch_async's. Only the first
+ *    d_n_moves[i] bytes of a moves slot are written; d_n_moves[i] == 0 flags a
+ *    triple whose walk came out of range or whose end key names no cell, and
+ *    d_ends of such a triple is unspecified.
+ * TSA_END_CORNER runs tsa_align_batch_async's own plan for `path` (tiled, strip
+ * or grid) and fills d_ends with the lengths, on the device. Under
+ * TSA_END_FACE and TSA_END_ANY a triple that fits one workgroup takes the
+ * resident kernel with its end search; every other one takes the tiled
+ * resident kernel's under TSA_ALIGN_PATH_TILED and the grid path's under
+ * TSA_ALIGN_PATH_GRID (forward over every tile with a key slot per tile, the
+ * end records, then backward from the end tile, x <= x1);
+ * TSA_ALIGN_PATH_STRIP is TSA_EINVAL. Overrides: align_tile holds; a set
+ * align_mode of tiled or grid replaces `path`; strip, resident or plane is
+ * TSA_EINVAL; align_tb_bytes caps a chunk's budget from above. A chunk raises
+ * tsa_kernel_launch_count as the synchronous entry point of its path does:
+ * [resident] + [tiled], or [resident] + max (nty+ntz-1) forward +
+ * max (nty+ntz-1) backward on the grid path; helper kernels and walks are not
+ * counted.
+ * The workspace is tsa_align_batch_async's; the end records lie on a region the
+ * end search leaves unused. On the grid path with a free end the fixed part has
+ * two more 256-byte-rounded regions: n int64 slot offsets and 8 bytes per tile
+ * of every over-capacity triple of the call (S = the sum of nty*ntz, whatever
+ * the chunks; they may hold anything on entry). So tsa_align_ends_workspace_size
+ * equals tsa_align_workspace_size under TSA_END_CORNER and under
+ * TSA_ALIGN_PATH_TILED, and exceeds it by up256(8n) + up256(8S) under
+ * TSA_ALIGN_PATH_GRID with a free end. It is host-only.
+ * Validation, all before any device work and in this order: TSA_EINVAL for a
+ * null pointer (d_ends included), a workspace that is not 256-byte aligned, an
+ * end_mode outside 0..2, whatever tsa_align_batch_async rejects, and the path
+ * and override combinations above; TSA_OK for n == 0; TSA_ENODEV; TSA_ENOMEM
+ * when workspace_bytes < min_bytes, with nothing queued.
+ * Not covered: a free end on the strip path, the plane sweep or tsa_align_gpu,
+ * and more than one device per call. */
+int tsa_align_ends_workspace_size(const int64_t *h_offsets, int32_t n, const tsa_params *p,
+                                  int32_t path, int32_t end_mode,
+                                  size_t *min_bytes, size_t *full_bytes);
+int tsa_align_batch_ends_async(const uint8_t *d_seqs, const int64_t *d_offsets,
+                               const int64_t *h_offsets, int32_t n, const tsa_params *p,
+                               int32_t path, int32_t end_mode, int32_t *d_scores,
+                               uint8_t *d_moves, int32_t *d_n_moves, int32_t *d_starts,
+                               int32_t *d_ends /* 3n */, void *d_workspace,
+                               size_t workspace_bytes, void *stream);
+
 /* The three gapped rows of n alignments, on the device (queues one launch on
  * stream, no synchronisation, no workspace). d_seqs and d_offsets as above;
  * d_moves, d_n_moves and d_starts in tsa_align_batch's layout, from
- * tsa_align_batch_async or uploaded from any of the synchronous entry points.
+ * tsa_align_batch_async, tsa_align_batch_ends_async or uploaded from any of the synchronous entry points.
  * d_rows has three times the layout of d_moves: triple i, of len_i = la+lb+lc
  * symbols, owns 3*len_i bytes at d_rows + 3*(offsets[3i] - offsets[0]), row r
  * (0 = A, 1 = B, 2 = C) at + r*len_i. The first d_n_moves[i] bytes of each row

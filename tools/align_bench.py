@@ -37,6 +37,16 @@ from the corner: a shared first half and unrelated second halves.
   python tools/align_bench.py --n 256 --la 128 --forms tiled --end corner,face,any
   python tools/align_bench.py --n 256 --la 128 --forms grid,tiled --end corner,face,any
   python tools/align_bench.py --n 8 --la 512 --forms grid --end corner,face,any --core-tails --tb-bytes 536870912
+--async together with --end adds, for the forms resident, tiled and grid, a leg
+through tsa_align_batch_ends_async per listed end mode
+(<form>_async_end_<mode>_ms), timed by the train and event scheme of the async
+leg, so one process holds the async corner leg (<form>_async_ms), the
+device-resident end-free legs and the synchronous ones; ends_async_agree says
+that every such leg returned what its synchronous leg returned, ends included.
+A library without tsa_align_batch_ends_async (the parent of a comparison) skips
+them.
+  python tools/align_bench.py --n 512 --la 64 --forms resident --async --end corner,face,any
+  python tools/align_bench.py --n 256 --la 128 --forms grid --async --end corner,face,any
 A library without tsa_align_batch (an older build named by TSA_PKG_DIR) runs
 the loop alone: that is how the baseline of a comparison is taken.
 Prints one JSON line: per form the median, min and max of the passes in ms."""
@@ -120,8 +130,9 @@ def main():
 
     dev = {}
 
-    def device_leg(mode):
-        """tsa_align_batch_async on device-resident inputs; returns (queue, results)."""
+    def device_leg(mode, end=None):
+        """tsa_align_batch_async (tsa_align_batch_ends_async with `end`) on
+        device-resident inputs; returns (results, timed)."""
         import torch
         if not dev:
             dev["seqs"], dev["offs"] = torch.from_numpy(seqs).cuda(), torch.from_numpy(offs).cuda()
@@ -129,12 +140,20 @@ def main():
                           torch.zeros(len(seqs), dtype=torch.uint8, device="cuda"),
                           torch.zeros(args.n, dtype=torch.int32, device="cuda"),
                           torch.zeros(3 * args.n, dtype=torch.int32, device="cuda"))
+            dev["ends"] = torch.zeros(3 * args.n, dtype=torch.int32, device="cuda")
         path = "tiled" if mode == "resident" else mode
-        ws_bytes = tsa.align_workspace_size(offs, path=path)[1]
+        ws_bytes = (tsa.align_workspace_size(offs, path=path) if end is None else
+                    tsa.align_ends_workspace_size(offs, path=path, end=end))[1]
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
         sc, mv, nm, st = dev["out"]
+        en = dev["ends"]
 
         def queue():
+            if end is not None:
+                tsa.align_batch_ends_async(dev["seqs"].data_ptr(), dev["offs"].data_ptr(), offs, sc.data_ptr(),
+                                           mv.data_ptr(), nm.data_ptr(), st.data_ptr(), en.data_ptr(), ws.data_ptr(),
+                                           ws_bytes, torch.cuda.current_stream().cuda_stream, path=path, end=end)
+                return
             tsa.align_batch_async(dev["seqs"].data_ptr(), dev["offs"].data_ptr(), offs, sc.data_ptr(), mv.data_ptr(),
                                   nm.data_ptr(), st.data_ptr(), ws.data_ptr(), ws_bytes,
                                   torch.cuda.current_stream().cuda_stream, path=path)
@@ -142,8 +161,9 @@ def main():
         def results():
             queue()
             torch.cuda.synchronize()
-            h = [t.cpu().numpy() for t in (sc, mv, nm, st)]
-            return [(int(h[0][i]), tuple(h[3][3 * i:3 * i + 3]), h[1][int(offs[3 * i]):int(offs[3 * i]) + int(h[2][i])])
+            h = [t.cpu().numpy() for t in (sc, mv, nm, st, en)]
+            return [(int(h[0][i]), tuple(h[3][3 * i:3 * i + 3]), h[1][int(offs[3 * i]):int(offs[3 * i]) + int(h[2][i])]) +
+                    ((tuple(h[4][3 * i:3 * i + 3]),) if end is not None else ())
                     for i in range(args.n)]
 
         def timed():
@@ -167,6 +187,9 @@ def main():
             for e in filter(None, args.end.split(",")):
                 if hasattr(tsa, "align_batch_ends") and (f != "grid" or "tsa_align_batch_grid_ends" in tsa.EXPORTS):
                     forms["%s_end_%s" % (f, e)] = batch_ends(f, e)
+                    if args.async_ and f in ("resident", "tiled", "grid") and hasattr(tsa, "align_batch_ends_async"):
+                        name = "%s_async_end_%s" % (f, e)
+                        forms[name], timers[name] = device_leg(f, e)
     out, refused = {}, {}
     for f, fn in list(forms.items()):                # first call: also the cross-check
         try:
@@ -179,6 +202,13 @@ def main():
     for f in names[1:]:
         for g, r in zip(out[f], out[names[0]]):
             same = same and g[0] == r[0] and tuple(g[1]) == tuple(r[1]) and bool((g[2] == r[2]).all())
+    ends_agree = None                                # every device-resident end leg against its synchronous leg
+    for f in out:
+        sync = f.replace("_async_end_", "_end_")
+        if "_async_end_" in f and sync in out:
+            ends_agree = ends_agree is not False and all(
+                g[0] == r[0] and tuple(g[1]) == tuple(r[1]) and bool((g[2] == r[2]).all()) and tuple(g[3]) == tuple(r[3])
+                for g, r in zip(out[f], out[sync]))
     times = {f: [] for f in forms}
     for k in range(args.warmup + args.passes):
         for f, fn in forms.items():
@@ -197,6 +227,8 @@ def main():
         res["tb_bytes"] = args.tb_bytes
     if timers:
         res["train"] = args.train
+    if ends_agree is not None:
+        res["ends_async_agree"] = ends_agree
     for f, why in refused.items():
         res[f + "_error"] = why
     for f, ts in times.items():
