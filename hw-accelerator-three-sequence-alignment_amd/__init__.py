@@ -70,6 +70,8 @@ EXPORTS = (
     "tsa_score_batch_ends_async", "tsa_describe_score_ends_plan", "tsa_align_batch_grid_ends",
     "tsa_score_batch_ends_ex", "tsa_score_ends_workspace_size_ex", "tsa_score_batch_ends_async_ex",
     "tsa_describe_score_ends_plan_ex", "tsa_align_ends_workspace_size", "tsa_align_batch_ends_async",
+    "tsa_score_batch_ends_lap", "tsa_score_ends_workspace_size_lap", "tsa_score_batch_ends_async_lap",
+    "tsa_describe_score_ends_plan_lap",
 )
 
 # Plan overrides the library accepts (tsa_set_override; include/trialign.h).
@@ -184,6 +186,10 @@ def _load_lib() -> ctypes.CDLL:
          ctypes.c_void_p]
     lib.tsa_describe_score_ends_plan_ex.argtypes = [ctypes.c_int32] * 4 + [pp, ctypes.c_int32, ctypes.c_int32,
                                                                           ctypes.c_char_p, ctypes.c_size_t]
+    lib.tsa_score_batch_ends_lap.argtypes = lib.tsa_score_batch_ends.argtypes
+    lib.tsa_score_ends_workspace_size_lap.argtypes = lib.tsa_score_ends_workspace_size.argtypes
+    lib.tsa_score_batch_ends_async_lap.argtypes = lib.tsa_score_batch_ends_async.argtypes
+    lib.tsa_describe_score_ends_plan_lap.argtypes = lib.tsa_describe_score_ends_plan.argtypes
     szp = ctypes.POINTER(ctypes.c_size_t)
     lib.tsa_align_workspace_size.argtypes = [i64p, ctypes.c_int32, pp, ctypes.c_int32, szp, szp]
     lib.tsa_align_batch_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, i64p, ctypes.c_int32, pp,
@@ -224,7 +230,9 @@ def _load_lib() -> ctypes.CDLL:
                  "tsa_score_ends_workspace_size", "tsa_score_batch_ends_async", "tsa_describe_score_ends_plan",
                  "tsa_align_batch_grid_ends", "tsa_score_batch_ends_ex", "tsa_score_ends_workspace_size_ex",
                  "tsa_score_batch_ends_async_ex", "tsa_describe_score_ends_plan_ex",
-                 "tsa_align_ends_workspace_size", "tsa_align_batch_ends_async"):
+                 "tsa_align_ends_workspace_size", "tsa_align_batch_ends_async", "tsa_score_batch_ends_lap",
+                 "tsa_score_ends_workspace_size_lap", "tsa_score_batch_ends_async_lap",
+                 "tsa_describe_score_ends_plan_lap"):
         getattr(lib, name).restype = ctypes.c_int
     return lib
 
@@ -531,6 +539,11 @@ def _ends_kernel(kernel) -> int:
     return KERNELS[kernel] if isinstance(kernel, str) else int(kernel)
 
 
+def _ends_lap(kernel) -> bool:
+    """``kernel="lap"``: the end search on the lap schedule (the tsa_*_lap entry points)."""
+    return isinstance(kernel, str) and kernel == "lap"
+
+
 def score_batch_ends(triples=None, params: Optional[TsaParams] = None, end: str | int = "any", device: int = 0,
                      seqs: Optional[np.ndarray] = None, offsets: Optional[np.ndarray] = None,
                      kernel: str | int | None = None) -> list:
@@ -549,7 +562,10 @@ def score_batch_ends(triples=None, params: Optional[TsaParams] = None, end: str 
     max_lc <= 256); ``"auto"`` takes the factored helix where it admits the
     request and the literal one otherwise, so it returns ``align_batch_ends``'s
     score and end for every parameter set within that shape; ``"pencil"`` is
-    the call above."""
+    the call above; ``"lap"`` (tsa_score_batch_ends_lap) runs the end search
+    of the checked int16 lap kernel, for the large cubes the helix forms refuse
+    (max_lc > 256: one 512^3 or 1024^3 cube, a handful of large ones), and
+    rescores what it cannot certify through ``align_batch_grid_ends``."""
     mode = _end_mode(end, "score_batch_ends")
     p = params or TsaParams.default()
     if seqs is None:
@@ -559,7 +575,12 @@ def score_batch_ends(triples=None, params: Optional[TsaParams] = None, end: str 
     n = (len(offsets) - 1) // 3
     sc = np.zeros(max(n, 1), dtype=np.int32)
     en = np.zeros(max(3 * n, 1), dtype=np.int32)
-    if kernel is None:
+    if _ends_lap(kernel):
+        rc = _lib.tsa_score_batch_ends_lap(_ptr(seqs, ctypes.c_uint8), _ptr(offsets, ctypes.c_int64), n,
+                                           ctypes.byref(p), mode, _ptr(sc, ctypes.c_int32), _ptr(en, ctypes.c_int32),
+                                           device)
+        _check(rc, "tsa_score_batch_ends_lap")
+    elif kernel is None:
         rc = _lib.tsa_score_batch_ends(_ptr(seqs, ctypes.c_uint8), _ptr(offsets, ctypes.c_int64), n, ctypes.byref(p),
                                        mode, _ptr(sc, ctypes.c_int32), _ptr(en, ctypes.c_int32), device)
         _check(rc, "tsa_score_batch_ends")
@@ -574,9 +595,15 @@ def score_batch_ends(triples=None, params: Optional[TsaParams] = None, end: str 
 def score_ends_workspace_size(n: int, max_la: int, max_lb: int, max_lc: int, params: Optional[TsaParams] = None,
                               end: str | int = "any", kernel: str | int | None = None) -> int:
     """Bytes of workspace ``score_batch_ends_async`` needs (tsa_score_ends_workspace_size;
-    with a ``kernel``, tsa_score_ends_workspace_size_ex)."""
+    with a ``kernel``, tsa_score_ends_workspace_size_ex; ``"lap"``,
+    tsa_score_ends_workspace_size_lap)."""
     p = params or TsaParams.default()
     sz = ctypes.c_size_t(0)
+    if _ends_lap(kernel):
+        _check(_lib.tsa_score_ends_workspace_size_lap(n, max_la, max_lb, max_lc, ctypes.byref(p),
+                                                      _end_mode(end, "score_ends_workspace_size"), ctypes.byref(sz)),
+               "tsa_score_ends_workspace_size_lap")
+        return int(sz.value)
     if kernel is not None:
         _check(_lib.tsa_score_ends_workspace_size_ex(n, max_la, max_lb, max_lc, ctypes.byref(p),
                                                      _end_mode(end, "score_ends_workspace_size"),
@@ -594,9 +621,17 @@ def score_batch_ends_async(d_seqs_ptr: int, d_offsets_ptr: int, n: int, max_la: 
                            params: Optional[TsaParams] = None, end: str | int = "any",
                            kernel: str | int | None = None) -> None:
     """Device-resident ``score_batch_ends`` (tsa_score_batch_ends_async; with a
-    ``kernel``, tsa_score_batch_ends_async_ex): raw device addresses, results
+    ``kernel``, tsa_score_batch_ends_async_ex; ``"lap"``,
+    tsa_score_batch_ends_async_lap): raw device addresses, results
     (n scores, 3n ends, int32) stay on the device."""
     p = params or TsaParams.default()
+    if _ends_lap(kernel):
+        rc = _lib.tsa_score_batch_ends_async_lap(
+            ctypes.c_void_p(d_seqs_ptr), ctypes.c_void_p(d_offsets_ptr), n, max_la, max_lb, max_lc, ctypes.byref(p),
+            _end_mode(end, "score_batch_ends_async"), ctypes.c_void_p(d_scores_ptr), ctypes.c_void_p(d_ends_ptr),
+            ctypes.c_void_p(d_ws_ptr), ctypes.c_size_t(ws_bytes), ctypes.c_void_p(stream_ptr))
+        _check(rc, "tsa_score_batch_ends_async_lap")
+        return
     if kernel is not None:
         rc = _lib.tsa_score_batch_ends_async_ex(
             ctypes.c_void_p(d_seqs_ptr), ctypes.c_void_p(d_offsets_ptr), n, max_la, max_lb, max_lc, ctypes.byref(p),
@@ -619,9 +654,15 @@ def describe_score_ends_plan(n: int, max_la: int, max_lb: int, max_lc: int, para
     the helix plan with ``ends=face`` or ``ends=any``, or ``describe_plan``'s text
     for the corner. Raises ``TsaError`` with the code the scoring call would return.
     With a ``kernel`` (tsa_describe_score_ends_plan_ex) the literal end search reads
-    ``plane literal-helix M=.. P=.. ends=..``."""
+    ``plane literal-helix M=.. P=.. ends=..``; ``kernel="lap"``
+    (tsa_describe_score_ends_plan_lap) reads ``pencil lap i16 .. ends=..``."""
     p = params or TsaParams.default()
     buf = ctypes.create_string_buffer(512)
+    if _ends_lap(kernel):
+        _check(_lib.tsa_describe_score_ends_plan_lap(n, max_la, max_lb, max_lc, ctypes.byref(p),
+                                                     _end_mode(end, "describe_score_ends_plan"), buf, len(buf)),
+               "tsa_describe_score_ends_plan_lap")
+        return buf.value.decode()
     if kernel is not None:
         _check(_lib.tsa_describe_score_ends_plan_ex(n, max_la, max_lb, max_lc, ctypes.byref(p),
                                                     _end_mode(end, "describe_score_ends_plan"),

@@ -47,13 +47,13 @@ constexpr int64_t LAP_MAX_WAVES = 4;
 // split over devices, whose parts may queue behind each other).
 // lit: the literal form (lap_kernel LIT: int16 shifted words, M <= 2).
 LapGeom lap_geom(int32_t n, int32_t max_la, int32_t max_lb, int32_t max_lc, int M, int NW,
-                 bool full_rings, bool f16, bool sop, bool lit = false);
+                 bool full_rings, bool f16, bool sop, bool lit = false, bool ends = false);
 // A batch of n triples as sequential launches of `chunk` triples each, so
 // that every launch's grid keeps to at most LAP_MAX_WAVES rounds: the
 // chunk of least total estimated latency (the lap_chunk override forces one, tests).
 // .ok = false when no chunk size fits.
 LapGeom lap_geom_chunked(int32_t n, int32_t max_la, int32_t max_lb, int32_t max_lc, int M, int NW, bool f16,
-                         bool sop, bool lit = false);
+                         bool sop, bool lit = false, bool ends = false);
 size_t lap_workspace_bytes(const LapGeom &g);
 // The launch's error word inside a workspace of n triples (set on a hand-off timeout).
 uint32_t *lap_err_word(const LapGeom &g, int32_t n, void *d_ws);
@@ -65,6 +65,21 @@ int lap_launch(const LapGeom &g, bool f16, bool sop, const uint8_t *d_seqs,
                const int64_t *d_offsets, int32_t n, int32_t *d_scores, void *d_ws,
                const PencilArgs &pa, hipStream_t stream, int32_t **d_err,
                const CheckLimits *chk = nullptr);
+
+// The end search (tsa_score_batch_ends_lap) on a geometry from lap_geom(...,
+// ends = true) -- the checked int16 form's, M <= 2, with the resident round
+// sized by lap_ends_kernel's own registers (lap_ends_simd_blocks_per_cu, from
+// the generated kernel table; 0 where the shape is not instantiated). The
+// workspace is lap_workspace_bytes(g) plus the key slots and may hold anything.
+// d_scores[i] the largest best over triple i's candidate cells (pa.end_face:
+// those on the end faces), d_ends[3i..3i+2] the cell (smallest x, then y, then
+// z among equals); TSA_SCORE_UNCERTIFIED outside *chk (null: no certification),
+// TSA_SCORE_INVALID after a timed-out hand-off, both with ends 0, 0, 0.
+int lap_ends_simd_blocks_per_cu(int M, int NW, bool sop);
+size_t lap_ends_workspace_bytes(const LapGeom &g);
+int lap_launch_ends(const LapGeom &g, bool sop, const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n,
+                    int32_t *d_scores, int32_t *d_ends, void *d_ws, const PencilArgs &pa, hipStream_t stream,
+                    int32_t **d_err, const CheckLimits *chk);
 
 // The literal form on a geometry from lap_geom(..., lit = true): the RTL's
 // wrapped arithmetic for any parameter set; d_final7 (may be null) receives

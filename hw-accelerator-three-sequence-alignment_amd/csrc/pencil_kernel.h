@@ -54,6 +54,25 @@ void pencil_describe_ends(int32_t max_la, int32_t max_lb, int32_t max_lc, const 
 int pencil_launch_ends(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, int32_t max_la,
                        int32_t max_lb, int32_t max_lc, const KParams &kp, const Range &bound, bool face,
                        int32_t *d_scores, int32_t *d_ends, void *d_ws, size_t ws_bytes, hipStream_t stream);
+// The end search on the lap schedule (tsa_score_batch_ends_lap under face and
+// any): the checked kernel's int16 plan with the key fold (lap_ends_kernel),
+// for a batch of n triples under policy `lap`. The admission (TSA_OK;
+// TSA_ERANGE where no lap plan of M <= 2 exists; TSA_EINVAL for a set
+// pencil_mode other than lap), the workspace (the checked lap workspace plus
+// the key slots), the plan as text, and the launch: results as
+// pencil_launch_ends', but TSA_SCORE_UNCERTIFIED for a triple outside *chk
+// (null: exact a priori, nothing is certified) and TSA_SCORE_INVALID after a
+// timed-out hand-off, both with ends 0, 0, 0. d_err as pencil_launch_batch's.
+int pencil_lap_ends_admit(int32_t n, int32_t max_la, int32_t max_lb, int32_t max_lc, const KParams &kp,
+                          LapPolicy lap);
+size_t pencil_lap_ends_workspace_bytes(int32_t n, int32_t max_la, int32_t max_lb, int32_t max_lc, const KParams &kp,
+                                       LapPolicy lap);
+void pencil_describe_lap_ends(int32_t n, int32_t max_la, int32_t max_lb, int32_t max_lc, const KParams &kp,
+                              LapPolicy lap, bool checked, bool face, char *buf, size_t len);
+int pencil_launch_lap_ends(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, int32_t max_la,
+                           int32_t max_lb, int32_t max_lc, const KParams &kp, bool face, int32_t *d_scores,
+                           int32_t *d_ends, void *d_ws, size_t ws_bytes, hipStream_t stream, LapPolicy lap,
+                           int32_t **d_err, const CheckLimits *chk);
 // The checked lap kernel (TSA_KERNEL_CHECKED) can run this batch: the lap
 // schedule is chosen for it (int16 arithmetic).
 bool pencil_checked_plan(int32_t n, int32_t max_la, int32_t max_lb, int32_t max_lc,

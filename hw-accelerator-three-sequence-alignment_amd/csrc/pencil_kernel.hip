@@ -226,8 +226,9 @@ static double helix_est(int32_t n, int32_t max_la, int32_t max_lb, int32_t max_l
 // consumer's producer is always running or done, and a producer never waits
 // for a consumer of a later round (boundary rings, lap_geom); every wait is
 // bounded.
+// ends: the end search's plan (lap_ends_kernel: int16, M <= 2, its own residency).
 static LapGeom lap_choice(int32_t n, int32_t max_la, int32_t max_lb, int32_t max_lc,
-                          LapPolicy lap, bool f16, bool sop, bool need = false) {
+                          LapPolicy lap, bool f16, bool sop, bool need = false, bool ends = false) {
   LapGeom none{};
   none.ok = false;
   if (lap == LAP_OFF || max_la > 4096 || max_la + 2 * 8 + 64 * 4 >= 8192) return none;
@@ -239,6 +240,7 @@ static LapGeom lap_choice(int32_t n, int32_t max_la, int32_t max_lb, int32_t max
   long v = 0;
   if (override_int("lap_m", &v)) m_lo = m_hi = (int)std::max(1L, std::min(4L, v));
   if (override_int("lap_nw", &v)) nw_lo = nw_hi = v == 4 ? 4 : 8;
+  if (ends) m_hi = std::min(m_hi, 2);  // z tiles cover any LC at M <= 2
   LapGeom best = none;
   for (int M = m_lo; M <= m_hi; M *= 2) {
     for (int NW = nw_lo; NW <= nw_hi; NW *= 2) {
@@ -247,7 +249,7 @@ static LapGeom lap_choice(int32_t n, int32_t max_la, int32_t max_lb, int32_t max
       // dispatcher ran round 2, two per CU started out of chain order and
       // timed out); a larger batch runs as chunks of triples, one launch
       // each (lap_geom_chunked)
-      const LapGeom g = lap_geom_chunked(n, max_la, max_lb, max_lc, M, NW, f16, sop);
+      const LapGeom g = lap_geom_chunked(n, max_la, max_lb, max_lc, M, NW, f16, sop, false, ends);
       if (!g.ok) continue;
       if (!best.ok || g.est_us < best.est_us) best = g;
     }
@@ -1399,6 +1401,59 @@ int pencil_launch_ends(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t 
                : launch_m<1, 8, true, false>(d_seqs, d_offsets, n, max_lb, g, d_scores, d_ws, pa, stream, d_ends);
   return sop ? launch_m<2, 8, true, true>(d_seqs, d_offsets, n, max_lb, g, d_scores, d_ws, pa, stream, d_ends)
              : launch_m<2, 8, true, false>(d_seqs, d_offsets, n, max_lb, g, d_scores, d_ws, pa, stream, d_ends);
+}
+
+// The end search on the lap schedule (tsa_score_batch_ends_lap, face and any):
+// always the checked kernel's int16 plan with the key fold (lap_ends_kernel),
+// never the helix. TSA_OK when a lap plan exists for the batch among the
+// instantiated geometries (M <= 2; lap_m, lap_nw and lap_chunk hold) and the
+// key's 16 bits hold x - 1; TSA_ERANGE otherwise; TSA_EINVAL for a set
+// pencil_mode other than lap.
+static LapGeom lap_ends_choice(int32_t n, int32_t max_la, int32_t max_lb, int32_t max_lc, const KParams &kp,
+                               LapPolicy lap) {
+  return lap_choice(n, max_la, max_lb, max_lc, lap, false, kp.s3_mode == TSA_S3_SOP, true, true);
+}
+int pencil_lap_ends_admit(int32_t n, int32_t max_la, int32_t max_lb, int32_t max_lc, const KParams &kp,
+                          LapPolicy lap) {
+  char mode[16] = "";
+  if (override_str("pencil_mode", mode, sizeof mode) && strcmp(mode, "lap")) return TSA_EINVAL;
+  if (!pencil_shape_ok(max_la, max_lb, max_lc) || max_la - 1 > 0xFFFE) return TSA_ERANGE;
+  return lap_ends_choice(n, max_la, max_lb, max_lc, kp, lap).ok ? TSA_OK : TSA_ERANGE;
+}
+
+size_t pencil_lap_ends_workspace_bytes(int32_t n, int32_t max_la, int32_t max_lb, int32_t max_lc, const KParams &kp,
+                                       LapPolicy lap) {
+  const LapGeom g = lap_ends_choice(n, max_la, max_lb, max_lc, kp, lap);
+  return g.ok ? lap_ends_workspace_bytes(g) : 0;
+}
+
+// pencil_describe's checked lap text with the end mode in place of the
+// estimate (lap_geom's is the plain score's); checked: certification runs
+void pencil_describe_lap_ends(int32_t n, int32_t max_la, int32_t max_lb, int32_t max_lc, const KParams &kp,
+                              LapPolicy lap, bool checked, bool face, char *buf, size_t len) {
+  const LapGeom lg = lap_ends_choice(n, max_la, max_lb, max_lc, kp, lap);
+  char chunk[32] = "";
+  if (lg.chunk > 0) snprintf(chunk, sizeof chunk, " chunk=%d", lg.chunk);
+  snprintf(buf, len, "pencil lap i16 %s M=%d NW=%d laps=%d tiles=%d waves=%lld wpc=%d%s%s ends=%s",
+           kp.s3_mode == TSA_S3_SOP ? "sop" : "rtl", lg.M, lg.NW, lg.G, lg.GZ, (long long)lg.waves, lg.per_cu, chunk,
+           checked ? " checked" : "", face ? "face" : "any");
+}
+
+int pencil_launch_lap_ends(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, int32_t max_la,
+                           int32_t max_lb, int32_t max_lc, const KParams &kp, bool face, int32_t *d_scores,
+                           int32_t *d_ends, void *d_ws, size_t ws_bytes, hipStream_t stream, LapPolicy lap,
+                           int32_t **d_err, const CheckLimits *chk) {
+  if (d_err) *d_err = nullptr;
+  if (n <= 0) return TSA_OK;
+  if (!d_ends) return TSA_EINVAL;
+  const int rc = pencil_lap_ends_admit(n, max_la, max_lb, max_lc, kp, lap);
+  if (rc) return rc;
+  const LapGeom lg = lap_ends_choice(n, max_la, max_lb, max_lc, kp, lap);
+  if (ws_bytes < lap_ends_workspace_bytes(lg)) return TSA_ENOMEM;
+  PencilArgs pa = make_args(kp, false, false);
+  pa.end_face = face ? 1 : 0;
+  return lap_launch_ends(lg, kp.s3_mode == TSA_S3_SOP, d_seqs, d_offsets, n, d_scores, d_ends, d_ws, pa, stream,
+                         d_err, chk);
 }
 
 int pencil_launch_batch(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n,

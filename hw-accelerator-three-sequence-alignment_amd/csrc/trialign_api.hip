@@ -1286,3 +1286,221 @@ int tsa_describe_score_ends_plan_ex(int32_t n, int32_t max_la, int32_t max_lb, i
 }
 
 }  // extern "C"
+
+// ---- end-free scores on the lap schedule (tsa_score_batch_ends_lap) ------------
+namespace {
+
+// A set pencil_mode other than lap rules the end search out (TSA_EINVAL, with
+// the other argument errors: before the n == 0 return).
+bool lap_ends_mode_ok() {
+  char mode[16] = "";
+  return !override_str("pencil_mode", mode, sizeof mode) || !strcmp(mode, "lap");
+}
+
+// Admission of a face / any request, host only: TSA_OK and *certify (the
+// factored form is checkable but not exact a priori, so lap_certify's rule
+// runs), TSA_ERANGE, or TSA_EINVAL for a set pencil_mode other than lap.
+int lap_ends_admit(int32_t n, int32_t max_la, int32_t max_lb, int32_t max_lc, const tsa_params *p, LapPolicy lap,
+                   bool *certify) {
+  if (!lap_ends_mode_ok()) return TSA_EINVAL;
+  const int kind = choose_kernel(TSA_KERNEL_CHECKED, p, max_la, max_lb, max_lc);
+  if (kind < 0) return TSA_ERANGE;
+  *certify = kind == TSA_KERNEL_CHECKED;
+  KParams kp;
+  if (build_kparams(p, &kp)) return TSA_EINVAL;
+  return pencil_lap_ends_admit(std::min(n, 65535), max_la, max_lb, max_lc, kp, lap);
+}
+
+// One triple of a host batch through tsa_align_batch_grid_ends' host path, the
+// moves discarded: literal arithmetic, any size, inside the pointer budget.
+int lap_ends_rescore(const uint8_t *seqs, const int64_t *o, const tsa_params *p, int32_t end_mode, int32_t device,
+                     int32_t *score, int32_t *end) {
+  std::vector<uint8_t> moves((size_t)std::max<int64_t>(o[3] - o[0], 1));
+  int32_t n_moves = 0, start[3] = {0, 0, 0};
+  return tsa_align_batch_grid_ends(seqs, o, 1, p, end_mode, score, moves.data(), &n_moves, start, end, device);
+}
+
+// A host batch on one device: chunks whose workspace stays under the cap of
+// run_host_batch_on_device, the lap plan of each (LAP_STREAM). A chunk's
+// uncertified triples, or all of it after a timed-out hand-off, are rescored
+// one by one (lap_ends_rescore).
+int run_host_lap_ends_on_device(int device, const uint8_t *seqs, const int64_t *offsets, int32_t n,
+                                int32_t max_la, int32_t max_lb, int32_t max_lc, const tsa_params *p,
+                                int32_t end_mode, bool certify, int32_t *scores, int32_t *ends) {
+  int rc = TSA_OK;
+  KParams kp;
+  if ((rc = build_kparams(p, &kp))) return rc;
+  const CheckLimits lim = certify ? check_limits(p) : CheckLimits{INT32_MAX, INT32_MIN};
+  const size_t cap = (size_t)8 << 30;
+  auto ws_of = [&](int32_t c) { return pencil_lap_ends_workspace_bytes(c, max_la, max_lb, max_lc, kp, LAP_STREAM); };
+  int32_t chunk = std::min(n, 65535);
+  while (chunk > 1 && ws_of(chunk) > cap) chunk = (chunk + 1) / 2;
+  const size_t ws_bytes = std::max(ws_of(chunk), n % chunk ? ws_of(n % chunk) : (size_t)0);
+  const int64_t base = offsets[0], nbytes = offsets[3 * (int64_t)n] - base;
+  uint8_t *d_seqs = nullptr;
+  int64_t *d_off = nullptr;
+  int32_t *d_scores = nullptr, *d_ends = nullptr;
+  void *d_ws = nullptr;
+  std::vector<int64_t> off((size_t)3 * n + 1);
+  std::vector<int32_t> redo;  // triples to rescore
+  hipStream_t s = nullptr;
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  for (size_t k = 0; k < off.size(); ++k) off[k] = offsets[k] - base;
+  if (hipMalloc(&d_seqs, std::max<int64_t>(nbytes, 1)) != hipSuccess ||
+      hipMalloc(&d_off, off.size() * sizeof(int64_t)) != hipSuccess ||
+      hipMalloc(&d_scores, (size_t)n * sizeof(int32_t)) != hipSuccess ||
+      hipMalloc(&d_ends, (size_t)n * 3 * sizeof(int32_t)) != hipSuccess ||
+      hipMalloc(&d_ws, std::max<size_t>(ws_bytes, 16)) != hipSuccess) {
+    rc = TSA_ENOMEM;
+    goto done;
+  }
+  HIPCHK(hipMemcpyAsync(d_seqs, seqs + base, nbytes, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(d_ws, 0, ws_bytes, s));
+  for (int32_t c0 = 0; c0 < n; c0 += chunk) {
+    const int32_t cn = std::min(chunk, n - c0);
+    int32_t *d_err = nullptr, herr = 0;
+    rc = pencil_launch_lap_ends(d_seqs, d_off + 3 * (int64_t)c0, cn, max_la, max_lb, max_lc, kp,
+                                end_mode == TSA_END_FACE, d_scores + c0, d_ends + 3 * (int64_t)c0, d_ws, ws_bytes, s,
+                                LAP_STREAM, &d_err, certify ? &lim : nullptr);
+    if (rc) goto done;
+    if (!d_err) {
+      rc = TSA_EINTERNAL;  // every plan of this call is a lap grid
+      goto done;
+    }
+    HIPCHK(hipMemcpyAsync(&herr, d_err, sizeof(herr), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(scores + c0, d_scores + c0, (size_t)cn * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(ends + 3 * (int64_t)c0, d_ends + 3 * (int64_t)c0, (size_t)cn * 3 * sizeof(int32_t),
+                          hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (herr) {
+      g_lap_fallbacks.fetch_add(1);
+      fprintf(stderr, "trialign: lap hand-off timed out on device %d (%d triples); rescoring by the grid "
+                      "traceback\n", device, cn);
+    }
+    for (int32_t i = c0; i < c0 + cn; ++i) {
+      if (scores[i] == TSA_SCORE_UNCERTIFIED && !herr) g_check_fallbacks.fetch_add(1);
+      if (herr || scores[i] == TSA_SCORE_UNCERTIFIED || scores[i] == TSA_SCORE_INVALID) redo.push_back(i);
+    }
+  }
+done:
+  if (s) (void)hipStreamSynchronize(s);
+  if (d_seqs) (void)hipFree(d_seqs);
+  if (d_off) (void)hipFree(d_off);
+  if (d_scores) (void)hipFree(d_scores);
+  if (d_ends) (void)hipFree(d_ends);
+  if (d_ws) (void)hipFree(d_ws);
+  if (s) (void)hipStreamDestroy(s);
+  for (size_t k = 0; k < redo.size() && rc == TSA_OK; ++k)
+    rc = lap_ends_rescore(seqs, offsets + 3 * (int64_t)redo[k], p, end_mode, device, scores + redo[k],
+                          ends + 3 * (int64_t)redo[k]);
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tsa_score_batch_ends_lap(const uint8_t *seqs, const int64_t *offsets, int32_t n, const tsa_params *p,
+                             int32_t end_mode, int32_t *scores, int32_t *ends, int32_t device) {
+  if (!seqs || !offsets || !scores || !ends || n < 0 || !params_ok(p)) return TSA_EINVAL;
+  if (end_mode < TSA_END_CORNER || end_mode > TSA_END_ANY) return TSA_EINVAL;
+  if (end_mode != TSA_END_CORNER && !lap_ends_mode_ok()) return TSA_EINVAL;
+  int32_t max_la = 0, max_lb = 0, max_lc = 0;
+  for (int32_t i = 0; i < n; ++i) {
+    const int64_t *o = offsets + 3 * (int64_t)i;
+    if (o[1] < o[0] || o[2] < o[1] || o[3] < o[2]) return TSA_EINVAL;
+    const int32_t la = (int32_t)(o[1] - o[0]), lb = (int32_t)(o[2] - o[1]), lc = (int32_t)(o[3] - o[2]);
+    const int rc = tsa_validate(seqs + o[0], la, seqs + o[1], lb, seqs + o[2], lc, p);
+    if (rc) return rc;
+    max_la = std::max(max_la, la);
+    max_lb = std::max(max_lb, lb);
+    max_lc = std::max(max_lc, lc);
+  }
+  if (n == 0) return TSA_OK;
+  if (end_mode == TSA_END_CORNER) {  // tsa_score_batch's own plan; the ends are the lengths
+    const int rc = tsa_score_batch_devices(seqs, offsets, n, p, scores, &device, 1);
+    if (rc) return rc;
+    for (int64_t j = 0; j < 3 * (int64_t)n; ++j) ends[j] = (int32_t)(offsets[j + 1] - offsets[j]);
+    return TSA_OK;
+  }
+  bool certify = false;
+  const int rc = lap_ends_admit(n, max_la, max_lb, max_lc, p, LAP_STREAM, &certify);
+  if (rc) return rc;
+  const int nd = tsa_device_count();
+  if (nd <= 0 || device < 0 || device >= nd) return TSA_ENODEV;
+  return run_host_lap_ends_on_device(device, seqs, offsets, n, max_la, max_lb, max_lc, p, end_mode, certify, scores,
+                                     ends);
+}
+
+int tsa_score_ends_workspace_size_lap(int32_t n, int32_t max_la, int32_t max_lb, int32_t max_lc,
+                                      const tsa_params *p, int32_t end_mode, size_t *bytes) {
+  if (!bytes || n < 0 || max_la < 1 || max_lb < 1 || max_lc < 1 || !params_ok(p)) return TSA_EINVAL;
+  if (end_mode < TSA_END_CORNER || end_mode > TSA_END_ANY) return TSA_EINVAL;
+  if (end_mode == TSA_END_CORNER)
+    return tsa_batch_workspace_size(n, max_la, max_lb, max_lc, p, TSA_KERNEL_CHECKED, bytes);
+  bool certify = false;
+  const int rc = lap_ends_admit(std::max(n, 1), max_la, max_lb, max_lc, p, LAP_RESIDENT, &certify);
+  if (rc) return rc;
+  KParams kp;
+  build_kparams(p, &kp);
+  *bytes = pencil_lap_ends_workspace_bytes(std::min(std::max(n, 1), 65535), max_la, max_lb, max_lc, kp, LAP_RESIDENT);
+  return TSA_OK;
+}
+
+int tsa_score_batch_ends_async_lap(const uint8_t *d_seqs, const int64_t *d_offsets, int32_t n, int32_t max_la,
+                                   int32_t max_lb, int32_t max_lc, const tsa_params *p, int32_t end_mode,
+                                   int32_t *d_scores, int32_t *d_ends, void *d_workspace, size_t workspace_bytes,
+                                   void *stream) {
+  if (!d_seqs || !d_offsets || !d_scores || !d_ends || !d_workspace || n < 0 || max_la < 1 || max_lb < 1 ||
+      max_lc < 1 || !params_ok(p))
+    return TSA_EINVAL;
+  if (end_mode < TSA_END_CORNER || end_mode > TSA_END_ANY) return TSA_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  if (end_mode == TSA_END_CORNER) {
+    const int rc = score_batch_async(d_seqs, d_offsets, n, max_la, max_lb, max_lc, p, TSA_KERNEL_CHECKED, d_scores,
+                                     d_workspace, workspace_bytes, stream, 0);
+    if (rc || n == 0) return rc;
+    hipLaunchKernelGGL(ends_fill_lengths, dim3((n + 255) / 256), dim3(256), 0, s, d_offsets, n, d_ends);
+    return hipGetLastError() == hipSuccess ? TSA_OK : TSA_EDEVICE;
+  }
+  if (!lap_ends_mode_ok()) return TSA_EINVAL;
+  if (n == 0) return TSA_OK;
+  bool certify = false;
+  int rc = lap_ends_admit(n, max_la, max_lb, max_lc, p, LAP_RESIDENT, &certify);
+  if (rc) return rc;
+  if (tsa_device_count() <= 0) return TSA_ENODEV;
+  KParams kp;
+  if ((rc = build_kparams(p, &kp))) return rc;
+  const int32_t chunk = std::min(n, 65535);
+  if (workspace_bytes < pencil_lap_ends_workspace_bytes(chunk, max_la, max_lb, max_lc, kp, LAP_RESIDENT))
+    return TSA_ENOMEM;
+  const CheckLimits lim = certify ? check_limits(p) : CheckLimits{INT32_MAX, INT32_MIN};
+  for (int32_t c0 = 0; c0 < n; c0 += chunk) {
+    const int32_t cn = std::min(chunk, n - c0);
+    rc = pencil_launch_lap_ends(d_seqs, d_offsets + 3 * (int64_t)c0, cn, max_la, max_lb, max_lc, kp,
+                                end_mode == TSA_END_FACE, d_scores + c0, d_ends + 3 * (int64_t)c0, d_workspace,
+                                workspace_bytes, s, LAP_RESIDENT, nullptr, certify ? &lim : nullptr);
+    if (rc) return rc;
+  }
+  return TSA_OK;
+}
+
+int tsa_describe_score_ends_plan_lap(int32_t n, int32_t max_la, int32_t max_lb, int32_t max_lc,
+                                     const tsa_params *p, int32_t end_mode, char *buf, size_t len) {
+  if (!buf || len == 0 || n < 1 || max_la < 1 || max_lb < 1 || max_lc < 1 || !params_ok(p)) return TSA_EINVAL;
+  if (end_mode < TSA_END_CORNER || end_mode > TSA_END_ANY) return TSA_EINVAL;
+  if (end_mode == TSA_END_CORNER)
+    return tsa_describe_plan(n, max_la, max_lb, max_lc, p, TSA_KERNEL_AUTO, 1, buf, len);
+  bool certify = false;
+  const int rc = lap_ends_admit(n, max_la, max_lb, max_lc, p, LAP_STREAM, &certify);
+  if (rc) return rc;
+  KParams kp;
+  build_kparams(p, &kp);
+  pencil_describe_lap_ends(std::min(n, 65535), max_la, max_lb, max_lc, kp, LAP_STREAM, certify,
+                           end_mode == TSA_END_FACE, buf, len);
+  return describe_overrides(buf, len);
+}
+
+}  // extern "C"

@@ -2,7 +2,7 @@
 // "TriAlign Score: <n>" (src/TriAlign_tb.sv:339-341).
 //   tsa A.dat B.dat C.dat [--kernel auto|plane|pencil] [--device N]
 //       [--s3 rtl|sop] [--bits B] [--match M --mismatch X --go O --ge E]
-//       [--states] [--align [--end corner|face|any] [--grid]] [--score-end face|any [--kernel plane|auto]]
+//       [--states] [--align [--end corner|face|any] [--grid]] [--score-end face|any [--kernel plane|auto | --lap]]
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -26,13 +26,16 @@ static int usage() {
           "                                     factored one where it admits the request and the literal one\n"
           "                                     otherwise (tsa_score_batch_ends_ex). With --kernel pencil or\n"
           "                                     --states a usage error)\n"
+          "           [--lap]   (with --score-end: the end search of the checked lap kernel, for cubes beyond\n"
+          "                      the helix forms (max_lc > 256), tsa_score_batch_ends_lap; with --kernel a\n"
+          "                      usage error)\n"
           "A/B/C: dat files (one symbol 0..4 per line) or FASTA (A=0 T=1 C=2 G=3 N=4)\n");
   return 2;
 }
 
 int main(int argc, char **argv) {
   const char *files[3];
-  int nf = 0, device = 0, kernel = TSA_KERNEL_AUTO, kernel_set = 0, states = 0, align = 0, grid = 0, end = TSA_END_CORNER, score_end = TSA_END_CORNER;
+  int nf = 0, device = 0, kernel = TSA_KERNEL_AUTO, kernel_set = 0, states = 0, align = 0, grid = 0, end = TSA_END_CORNER, score_end = TSA_END_CORNER, lap = 0;
   tsa_params p;
   tsa_default_params(&p);
   for (int i = 1; i < argc; ++i) {
@@ -53,6 +56,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(a, "--states")) states = 1;
     else if (!strcmp(a, "--align")) align = 1;
     else if (!strcmp(a, "--grid")) grid = 1;
+    else if (!strcmp(a, "--lap")) lap = 1;
     else if (!strcmp(a, "--end")) {
       const char *v = next();
       if (!v) return usage();
@@ -74,6 +78,7 @@ int main(int argc, char **argv) {
   }
   if (nf != 3 || ((end != TSA_END_CORNER || grid) && !align)) return usage();
   if (score_end != TSA_END_CORNER && (align || states || (kernel_set && kernel == TSA_KERNEL_PENCIL))) return usage();
+  if (lap && (score_end == TSA_END_CORNER || kernel_set)) return usage();
   uint8_t *s[3];
   int64_t n[3];
   for (int k = 0; k < 3; ++k) {
@@ -89,6 +94,7 @@ int main(int argc, char **argv) {
     if (seqs)
       for (int k = 0; k < 3; ++k) memcpy(seqs + off[k], s[k], (size_t)n[k]);
     const int rc = !seqs ? TSA_ENOMEM
+                   : lap      ? tsa_score_batch_ends_lap(seqs, off, 1, &p, score_end, &score, en, device)
                    : kernel_set ? tsa_score_batch_ends_ex(seqs, off, 1, &p, score_end, kernel, &score, en, device)
                                 : tsa_score_batch_ends(seqs, off, 1, &p, score_end, &score, en, device);
     free(seqs);

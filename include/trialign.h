@@ -520,6 +520,66 @@ int tsa_describe_score_ends_plan_ex(int32_t n, int32_t max_la, int32_t max_lb,
                                     int32_t end_mode, int32_t kernel, char *buf,
                                     size_t len);
 
+/* The same four on the lap schedule, for the cubes the two families above
+ * refuse (max_lc > 256: one 512^3 or 1024^3 cube, a handful of large ones):
+ * scores[i] and ends[3i..3i+2] exactly as tsa_align_batch_ends defines them,
+ * found by the checked int16 lap kernel as it sweeps (lap_ends_kernel: every
+ * register half keeps one key {best : ~(x - 1)} of its candidate cells, a
+ * reduction kernel takes the triple's largest), with no memory per cell.
+ * Layouts, validation order and thread safety are tsa_score_batch_ends'.
+ * Errors, in this order and before any device work: TSA_EINVAL for a null
+ * pointer (ends included), bad offsets, symbols or parameters, an end_mode
+ * outside 0..2, or (under face and any) a set pencil_mode other than lap;
+ * TSA_OK for n == 0; TSA_ERANGE for a request the admission below refuses;
+ * TSA_ENODEV.
+ *
+ * TSA_END_CORNER runs tsa_score_batch's own plan (on the async call
+ * tsa_score_batch_async's under TSA_KERNEL_CHECKED, with
+ * tsa_batch_workspace_size's workspace for that kernel) and fills ends with
+ * the lengths. Under TSA_END_FACE and TSA_END_ANY a request is admitted exactly
+ * when TSA_KERNEL_CHECKED admits (max_la, max_lb, max_lc) -- the factored form
+ * is exact a priori, or its int16 carrier holds the a-priori bound and only the
+ * SCORE_BITS wrap has to be ruled out by the certificate -- and a lap plan
+ * exists for (n, maxima) among the end search's geometries (M = 1, 2 pairs per
+ * lane, NW = 4, 8 waves; chunked as the score plans are). The call never runs
+ * the helix, the literal forms or the split over devices; lap_m, lap_nw,
+ * lap_chunk and lap_spin_limit hold. Where the form is exact a priori nothing
+ * is certified; where it is only checkable the checked kernel's rule runs, and
+ * a certified triple's result is exact because no value of its cube wraps.
+ *
+ * A triple that is not certified reads TSA_SCORE_UNCERTIFIED on the async call,
+ * one whose launch had a hand-off time out TSA_SCORE_INVALID, both with ends
+ * 0, 0, 0. The synchronous call rescores such triples through
+ * tsa_align_batch_grid_ends' host path (literal arithmetic, any size) and
+ * discards the moves: tsa_check_fallback_count rises by one per uncertified
+ * triple, tsa_fallback_count once per chunk that timed out.
+ *
+ * The workspace is the checked lap workspace of the geometry plus the key
+ * slots, 8 bytes per compute wave of every logical workgroup
+ * (tsa_score_ends_workspace_size_lap, host-only; it may hold anything on
+ * entry). tsa_kernel_launch_count rises by one per lap launch. The plan text is
+ * the checked lap plan's with " ends=face" or " ends=any" in place of the
+ * estimate (" checked" where certification runs), and tsa_describe_plan's
+ * (synchronous, TSA_KERNEL_AUTO) for the corner.
+ *
+ * Not covered: an end search on the literal lap, on a cube split over devices,
+ * the M = 4 geometries, and more than one device per call. */
+int tsa_score_batch_ends_lap(const uint8_t *seqs, const int64_t *offsets, int32_t n,
+                             const tsa_params *p, int32_t end_mode, int32_t *scores,
+                             int32_t *ends /* 3n */, int32_t device);
+int tsa_score_ends_workspace_size_lap(int32_t n, int32_t max_la, int32_t max_lb,
+                                      int32_t max_lc, const tsa_params *p,
+                                      int32_t end_mode, size_t *bytes);
+int tsa_score_batch_ends_async_lap(const uint8_t *d_seqs, const int64_t *d_offsets,
+                                   int32_t n, int32_t max_la, int32_t max_lb,
+                                   int32_t max_lc, const tsa_params *p,
+                                   int32_t end_mode, int32_t *d_scores,
+                                   int32_t *d_ends, void *d_workspace,
+                                   size_t workspace_bytes, void *stream);
+int tsa_describe_score_ends_plan_lap(int32_t n, int32_t max_la, int32_t max_lb,
+                                     int32_t max_lc, const tsa_params *p,
+                                     int32_t end_mode, char *buf, size_t len);
+
 /* Device-resident traceback: tsa_align_batch on sequences that are already in
  * device memory, with results that stay there. d_* are device pointers on the
  * current device, stream is a hipStream_t (NULL = default stream). h_offsets

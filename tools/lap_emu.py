@@ -20,6 +20,12 @@ Layout (one workgroup = one (lap L, z-tile q) of a triple):
     REC = {above.hi -> lo, own_prev.lo -> hi} per record word;
   * z-1 neighbours: registers shift up one position per step; position 0
     takes the previous tile's last position, record t + ZT of that tile.
+
+emulate(..., end="any" | "face") replays the end search of lap_ends_kernel
+(tsa_score_batch_ends_lap) on the same schedule: y and z of a register half are
+fixed for the lap and only x moves, so a half keeps one key {best, smaller x},
+a lane widens it by its row and position, a wave's largest goes to its slot
+and the triple's result is the largest slot (tests/test_score_ends_lap.py).
 """
 from __future__ import annotations
 
@@ -62,11 +68,44 @@ def vs_cell(X, Y, Z, XY, YZ, XZ, Mv, lam, cP, dO):
             np.maximum(Y, NXY), np.maximum(Y, NYZ), np.maximum(Y - dO, NXZ))
 
 
-def emulate(a, b, c, match=1, mismatch=-1, go=2, ge=1, sop=False, NW=2, M=1, SK=1, cells=None, vs=False):
+END_GARBAGE = 0x7F00   # planted in best of every cell that is no candidate: it wins any fold it enters
+
+
+def end_key(best, xm1):
+    """The end search's 32-bit key of one candidate (lap_kernel END):
+    {best ^ 0x8000 : 0xFFFF - (x - 1)} -- the larger score, then the smaller x."""
+    return (((int(best) & 0xFFFF) ^ 0x8000) << 16) | ((0xFFFF - int(xm1)) & 0xFFFF)
+
+
+def end_key64(key, y0, z0):
+    """A lane's key widened by the 0-based row and position: ~y, then ~z."""
+    return (int(key) << 32) | ((0xFFFF - y0) << 16) | (0xFFFF - z0)
+
+
+def end_decode(key64):
+    """(score, (x, y, z)) of a 64-bit key (lap_ends_reduce)."""
+    v = ((key64 >> 48) & 0xFFFF) ^ 0x8000
+    score = v - 0x10000 if v & 0x8000 else v
+    return score, tuple(0xFFFF - ((key64 >> sh) & 0xFFFF) + 1 for sh in (32, 16, 0))
+
+
+def emulate(a, b, c, match=1, mismatch=-1, go=2, ge=1, sop=False, NW=2, M=1, SK=1, cells=None, vs=False,
+            end=None, max_lens=None):
     """Score of one triple by the lap schedule (no wrap: valid where the
     factored form is exact). vs: the V-space cell (lap_kernel VS: values
     shifted by lam (x+y+z), lam = GE = -MISMATCH) with its face values --
-    x = 1 injection, lap 0's y = 0 records, tile 0's z = 0 records."""
+    x = 1 injection, lap 0's y = 0 records, tile 0's z = 0 records.
+
+    end = "any" | "face" (or a tuple of them): the end search of lap_ends_kernel
+    instead -- (score, (x, y, z)) per mode. Every step folds best into one key per
+    register half under the kernel's x mask (xlo <= x - 1 <= la - 1), the row
+    and position masks are applied when a lane widens its keys, a wave's largest
+    goes to its slot and the triple's result is the largest slot. The fold sees
+    END_GARBAGE in best of every cell that is no candidate by its coordinates
+    -- cells not yet started, drain cells past x = la, padding rows and
+    positions, and under face the cells off the end faces -- so a mask error
+    shows. max_lens: the geometry of a batch's maxima (slots of laps and tiles
+    this triple does not have keep the neutral fill)."""
     lam = ge if vs else 0
     assert not vs or ge == -mismatch
     cP, dO, dm = go + mismatch + lam, go - ge, match - mismatch
@@ -74,6 +113,11 @@ def emulate(a, b, c, match=1, mismatch=-1, go=2, ge=1, sop=False, NW=2, M=1, SK=
     P = penalties(go, ge)
     RW, ZT = 2 * NW, 64 * M
     G, GZ = -(-lb // RW), -(-lc // ZT)
+    modes = () if end is None else (end,) if isinstance(end, str) else tuple(end)
+    assert not (modes and (vs or SK != 1)) and all(m in ("any", "face") for m in modes)
+    mlb, mlc = (lb, lc) if max_lens is None else (max_lens[1], max_lens[2])
+    Gm, GZm = -(-mlb // RW), -(-mlc // ZT)
+    slots = {m: [0] * (Gm * GZm * NW) for m in modes}   # the launch's neutral fill
     f_single = -int(P[1].min())
     f_pair = -int(P[4].min())
     face = (f_single, f_pair, f_pair, 0)          # y = 0 face record {Iy, Ixy, Iyz, best}
@@ -138,6 +182,7 @@ def emulate(a, b, c, match=1, mismatch=-1, go=2, ge=1, sop=False, NW=2, M=1, SK=
                     svM[0, w, 0, 0] = r2[3]
             ys, zs = [], []
             out_hist = []
+            ekey = {m: np.zeros((NW, M, 64, 2), np.int64) for m in modes}
             for t in range(T):
                 PH = t & 1
                 out_now = np.zeros_like(out_prev)
@@ -214,6 +259,18 @@ def emulate(a, b, c, match=1, mismatch=-1, go=2, ge=1, sop=False, NW=2, M=1, SK=
                                     if 1 <= x <= la and y <= lb and z <= lc:
                                         cells[(x, y, z)] = S[:, i, l, h].copy()
                     best = msg[0]
+                    for m in modes:   # ---- the end search's fold of this step
+                        rowi2 = (L * RW + 2 * w + np.arange(2))[None, None, :]
+                        zpos = (q * ZT + kpos)[:, :, None]
+                        on_face = (rowi2 == lb - 1) | (zpos == lc - 1)
+                        xlo = np.where(on_face, 0, la - 1) if m == "face" else np.zeros((M, 64, 2), np.int64)
+                        cand = np.clip(u, xlo, la - 1) == u           # the kernel's mask: x alone
+                        real = (u >= 0) & (u < la) & (rowi2 < lb) & (zpos < lc)
+                        if m == "face":
+                            real &= (u == la - 1) | on_face
+                        seen = np.where(real, best, END_GARBAGE)
+                        keys = (((seen & 0xFFFF) ^ 0x8000) << 16) | ((0xFFFF - u) & 0xFFFF)   # end_key, every half
+                        ekey[m][w] = np.maximum(ekey[m][w], np.where(cand, keys, 0))
                     nIx, oIy, oIz, oIxy, oIyz, oIxz = msg[1], msg[2], msg[3], msg[4], msg[5], msg[6]
                     out = np.stack([oIy, oIxy, oIyz, best])
                     out_now[:, w] = out
@@ -257,6 +314,17 @@ def emulate(a, b, c, match=1, mismatch=-1, go=2, ge=1, sop=False, NW=2, M=1, SK=
                 zs.append(zstep)
             yrec[(L, q)] = ys
             zrec[(L, q)] = zs
+            for m in modes:   # a lane widens its keys (row and position masks), the wave reduces them
+                for w in range(NW):
+                    bk = 0
+                    for i, l, h in zip(*np.nonzero(ekey[m][w])):
+                        yy, k = L * RW + 2 * w + int(h), M * int(l) + int(i)
+                        if yy < lb and k < zt_q:
+                            bk = max(bk, end_key64(ekey[m][w][i, l, h], yy, q * ZT + k))
+                    slots[m][(L * GZm + q) * NW + w] = bk
+    if modes:
+        res = tuple(end_decode(max(slots[m])) for m in modes)
+        return res[0] if isinstance(end, str) else res
     return score
 
 

@@ -15,6 +15,14 @@ cost of the end search is read against the corner leg of the same pass.
 literal helix score (tsa_score_batch_async, TSA_KERNEL_PLANE under
 pencil_mode=literal), the face and any legs its end search
 (tsa_score_batch_ends_async_ex, TSA_KERNEL_PLANE).
+  python tools/score_ends_bench.py --lap --n 1 --L 1024 --out profiles/score_ends_lap.jsonl
+  python tools/score_ends_bench.py --lap --n 8 --L 512 --grid --out profiles/score_ends_lap.jsonl
+--lap times the end search of the lap schedule (tsa_score_batch_ends_async_lap)
+on a few large cubes: the corner leg is the checked (or, where the factored
+form is exact a priori, the plain) lap score of the same cubes
+(tsa_score_batch_async, TSA_KERNEL_CHECKED). --grid adds, per pass, one
+synchronous tsa_align_batch_grid_ends call (any) on the same cubes, timed on
+the host clock: the free-end answer these cubes had before.
 Prints one JSON line per process (every pass's figures, and per leg the median,
 min and max in ms) and appends it to --out when given. The first call of each
 leg is also a check: the corner leg equals tsa_score_batch_ends' corner mode,
@@ -38,12 +46,15 @@ def main():
     ap.add_argument("--train", type=int, default=20)
     ap.add_argument("--kernel", choices=("pencil", "plane"), default="pencil",
                     help="pencil: the factored helix (default); plane: the literal helix and its end search")
+    ap.add_argument("--lap", action="store_true", help="the lap schedule: checked lap score, tsa_*_ends_*_lap")
+    ap.add_argument("--grid", action="store_true", help="with --lap: also one tsa_align_batch_grid_ends call per pass")
     ap.add_argument("--out", default=None, help="append the JSON line to this file")
     args = ap.parse_args()
     import bench
     tsa = bench.load_pkg()
-    kernel = args.kernel
-    ends_kernel = None if kernel == "pencil" else kernel      # None: the entry points without a kernel argument
+    kernel = "checked" if args.lap else args.kernel
+    # None: the entry points without a kernel argument
+    ends_kernel = "lap" if args.lap else None if kernel == "pencil" else kernel
     if kernel == "plane":
         tsa.set_override("pencil_mode", "literal")            # the literal helix for every leg, whatever the cost model
     import torch
@@ -96,10 +107,17 @@ def main():
             t1.record()
             t1.synchronize()
             row[name] = round(t0.elapsed_time(t1) / args.train, 4)
+        if args.lap and args.grid:   # the grid traceback with a free end: a synchronous host call
+            import time
+            torch.cuda.synchronize()
+            w0 = time.perf_counter()
+            grid_res = tsa.align_batch_ends(seqs=seqs, offsets=offs, end="any", grid=True)
+            row["grid_any_host"] = round((time.perf_counter() - w0) * 1e3, 3)
+            ok = ok and [r[0] for r in grid_res] == h["any"].tolist()
         passes.append(row)
     res = {"bench": "score_ends", "kernel": kernel, "n": n, "shape": [L, L, L], "train": args.train, "warmup": args.warmup,
-           "passes": passes, "plans": plans, "legs_consistent": ok, "version": tsa.version(), "pid": os.getpid()}
-    for name in legs:
+           "passes": passes, "plans": plans, "legs_consistent": ok, "lap": bool(args.lap), "version": tsa.version(), "pid": os.getpid()}
+    for name in list(legs) + (["grid_any_host"] if args.lap and args.grid else []):
         ts = [p[name] for p in passes]
         res[name + "_ms"] = {"median": round(statistics.median(ts), 4), "min": min(ts), "max": max(ts)}
     for name in ("face", "any"):
